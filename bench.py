@@ -12,10 +12,16 @@ One "step" = one FurnitureEnv.step() on every env = 50 physics substeps + connec
     python bench.py --config 4 --gpus 8  # BASELINE configs: 2 (default), 3 Sawyer + swivel_chair 8192 envs, 4 Baxter + desk_mikael,
                                          # 5 mixed-furniture batch (table_lack / chair_agne / shelf_ivar per lane)
 
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full                # + the figures below
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    # + the last timed step's outputs as DIR/<name>.npy
+
 Rank 0 prints ONE JSON line.  `value` is the whole-job aggregate; inputs are resident in HBM when the timed region
-starts (actions are generated on the device).  `roofline` prices the fused step kernel against HBM peak with the
-algorithmic bytes of SURVEY.md section 8(d); `cpu_baseline` times the CPU checker (oracle/, a C port of the same
-pipeline) on the host cores with the same protocol -- a reported baseline, not the target.
+starts (actions are generated on the device).  A plain run sets up, warms up, times --steps steps and prints that line;
+everything else it can measure or check runs with --full only: `roofline` prices the fused step kernel (HIP-event
+timed in the same window) against HBM peak with the algorithmic bytes of SURVEY.md section 8(d); `config.episode_window`
+is a second timed window spanning a full episode; `cpu_baseline` times the CPU checker (oracle/, a C port of the same
+pipeline) on the host cores with the same protocol -- a reported baseline, not the target; `config.obs_finite` and
+`config.envs_that_dropped_contacts` check the outputs.
 """
 import argparse
 import json
@@ -35,6 +41,7 @@ AGENT, FURNITURE = "Sawyer", "table_lack_0825"
 MAX_EPISODE_STEPS = 150
 SEED = int(os.environ.get("FSIM_BENCH_SEED", "123"))  # (development: workload-realisation noise; the benchmark seed is 123)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: above this, a fixed seeded sample of env rows is written
 # SURVEY.md section 8(d), fused formulation, fp32: in = state 122 w + per-env mutable model 99 w + action 9 w,
 # out = state 122 w + mutable model 99 w + obs 64 w + reward/done/info ~8 w  -> 523 words per env-step
 ALGO_BYTES_PER_ENV_STEP = 523 * 4
@@ -169,6 +176,32 @@ def cpu_baseline(seconds=10.0, kind="native"):
                       "logic of the oracle env" % (cores, seconds, steps / wall / cores, 100 * (share or 0))}
 
 
+def host_outputs(obs, reward, done, info=None):
+    """What the timed path hands its caller after a step, as host float arrays (one row per env): obs (bf16 widened to fp32), reward,
+    done as 0 / 1, and info with its float-bit columns (include/fsim.h FSIM_INFO_*_F) decoded -- every value exact."""
+    out = {"obs": obs.float().cpu().numpy(), "reward": reward.float().cpu().numpy(), "done": done.float().cpu().numpy()}
+    if info is not None:
+        from furniture_amd.sim import INFO_CTRL_PENALTY_F, INFO_EPISODE_REWARD_F, INFO_SUCCESS_REWARD_F
+        raw = info.cpu().numpy()
+        cols = list(range(INFO_SUCCESS_REWARD_F, INFO_CTRL_PENALTY_F + 1)) + [INFO_EPISODE_REWARD_F]
+        out["info"] = raw.astype(np.float64)
+        out["info"][:, cols] = raw[:, cols].view(np.float32)
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array.  Above DUMP_BUDGET_BYTES the same seeded sample of rows is taken from every
+    array, and the sampled env indices are written as env_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(arrays["obs"])
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n + 8
+    if row_bytes * n > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.RandomState(0).choice(n, (DUMP_BUDGET_BYTES - 4096) // row_bytes, replace=False))  # (4 KB: the .npy headers)
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, env_rows=rows.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -241,11 +274,13 @@ def mixed_bench(args):
         dist.barrier()
     t0 = time.perf_counter()
     for t in range(args.warmup, args.warmup + args.steps):
-        env.step(acts[t]); env.gather()
+        env.step(acts[t]); out = env.gather()
     torch.cuda.synchronize(env.device)
     if distributed:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, host_outputs(*out))
     if distributed:
         tt = torch.tensor([dt], device=env.device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -279,15 +314,18 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline", choices=["native", "python"], default="native", help="native: oracle/libfsim_cpu.so (C env logic + physics behind the same C-ABI, OpenMP); python: oracle/oracle_env.py, one process per core")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: roofline (HIP-event kernel timing), the episode window, the CPU baseline, obs / contact checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned (obs, reward, done, info) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="(with --full) how long the CPU baseline runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) leave the CPU baseline out")
+    ap.add_argument("--cpu-baseline", choices=["native", "python"], default="native", help="(with --full) native: oracle/libfsim_cpu.so (C env logic + physics behind the same C-ABI, OpenMP); python: oracle/oracle_env.py, one process per core")
     ap.add_argument("--agent", default=AGENT, help="(exploration only; the benchmark workload is the default)")
     ap.add_argument("--furniture", default=FURNITURE, help="(exploration only)")
     ap.add_argument("--dense", action="store_true", help="(exploration only) FurnitureSawyerDenseRewardEnv: 8-phase dense reward + its config overrides")
     ap.add_argument("--control-type", default="impedance", help="(exploration only) a torque-level arm controller, e.g. position_orientation")
     ap.add_argument("--episode-window", type=int, default=-1,
-                    help="steps of a SECOND, un-headlined timed window run after the contract's (reported as config.episode_window_*): -1 = one full "
+                    help="(with --full) steps of a SECOND, un-headlined timed window run after the contract's (reported as config.episode_window_*): -1 = one full "
                          "episode + 10 steps when --steps is shorter than an episode, 0 = off")
     ap.add_argument("--obs-bf16", action="store_true", help="store the observation slab as bfloat16 (BASELINE config 2's narrow slab; state stays fp32)")
     ap.add_argument("--no-lookahead", action="store_true", help="(exploration only) resets run inside the terminal step's launch instead of ahead of time (fsim_config_t::lookahead_reset = 0)")
@@ -296,7 +334,7 @@ def main():
                     help="env groups (slabs) per GPU, each a handle of its own, stepped asynchronously (1 = one synchronous launch)")
     ap.add_argument("--threads", type=int, default=int(os.environ.get("FSIM_BENCH_THREADS", "1")), choices=[0, 1],
                     help="1 (default since round 6; single-process runs only): one host thread per slab -- each slab is re-stepped as soon as ITS step is "
-                         "done (+1 %: 836 / 834 k against 826 / 828 k on one box, profiles/r06_b_*); 0: one thread, round robin (what a rank under torch.distributed.run does)")
+                         "done (+1 %%: 836 / 834 k against 826 / 828 k on one box, profiles/r06_b_*); 0: one thread, round robin (what a rank under torch.distributed.run does)")
     args = ap.parse_args()
     # the host-side reset-table sampler (libfsim_host.so) is OpenMP code; with one host thread per slab, G of its parallel regions start at
     # once when a batch-wide episode end reaches every slab: G x all-cores threads spinning on 64 cores took tens of seconds
@@ -429,7 +467,8 @@ def main():
 
     # U(-1,1) actions of every step, generated on the device BEFORE the timed region (the contract: inputs resident in HBM when
     # the clock starts) -- one slab-step's actions are a [ng, dof] slice; no torch kernel is launched inside the loop, where it
-    # would queue behind the step kernels' waves for up to a millisecond
+    # would queue behind the step kernels' waves for up to a millisecond.  The episode window's rows are drawn with or without --full:
+    # the values torch's generator puts in a row depend on the tensor's size, and the timed steps see the same actions either way
     ew_steps = args.episode_window if args.episode_window >= 0 else (MAX_EPISODE_STEPS + 10 if args.steps < MAX_EPISODE_STEPS else 0)
     total_steps = args.warmup + args.steps + ew_steps
     for sl in slabs:
@@ -506,8 +545,9 @@ def main():
     run_steps(args.warmup)
     drain()
     la0 = [sl.sim.lookahead_stats() for sl in slabs]
-    for sl in slabs:
-        sl.sim.kernel_time_ms()  # reset the accumulators
+    if args.full:
+        for sl in slabs:
+            sl.sim.kernel_time_ms()  # switches the HIP-event timing of every step launch on (and resets its accumulators)
     if distributed:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -518,12 +558,15 @@ def main():
     if distributed:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # (slab order; under RCCL obs / reward / done are the gathered ones, and info, not gathered, is left out)
+        outs = [host_outputs(*sl.gathered, None if distributed else sl.info) for sl in slabs]
+        dump_outputs(args.dump_outputs, {k: np.concatenate([o[k] for o in outs]) for k in outs[0]})
     la_mid = [sl.sim.lookahead_stats() for sl in slabs]
-    kt = [sl.sim.kernel_time_ms() for sl in slabs]  # (of the contract's timed region: read before the second window adds its launches)
+    kt = [sl.sim.kernel_time_ms() for sl in slabs] if args.full else None  # (of the contract's timed region: read before the second window adds its launches)
     # Second window, NOT the headline: the contract's K steps after a reset contain no episode end (150-step episodes), so no reset and no
     # look-ahead reset work; this one spans a full episode right behind it -- every env resets once inside it -- on the same clock rules.
     ew = None
-    if ew_steps > 0:
+    if args.full and ew_steps > 0:
         if distributed:
             dist.barrier()
         torch.cuda.synchronize(dev)
@@ -545,59 +588,17 @@ def main():
               "resets": d_["swapped"] + d_["inline"], "resets_taken_from_lookahead": d_["swapped"], "reset_substeps": d_["units"] + d_["inline"] * reset_sub,
               "note": "a second timed window right behind the contract's, spanning one full episode (every env resets once inside it); per-rank counts"}
     la1 = la_mid
-    # envs whose record carries the sticky contact-overflow word (fsim_model.hpp E_OVERFLOW): some launch since the handle was created
-    # -- warm-up included -- needed more contact slots than the kernel's LDS image holds and dropped the rest for that substep
-    from furniture_amd.sim import E_OVERFLOW
-    dropped = int(sum(int((sl.sim.get_state("env_block")["env_block"].view(torch.int32)[:, E_OVERFLOW] != 0).sum()) for sl in slabs))
     la = {k: sum(b[k] - a[k] for a, b in zip(la0, la1)) for k in ("units", "swapped", "inline")}
     reset_substeps = 401 if m.meta.get("has_recipe") else 301  # sim.step() calls of one _reset (tests/golden/reset_trace.npz)
-    klaunches = sum(k[1] for k in kt)
-    kms = sum(k[0] * k[1] for k in kt) / max(1, klaunches)
     units_per_launch = ng  # env-steps one launch of the dominant kernel processes
     if distributed:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
-    obs = torch.cat([sl.obs for sl in slabs])
-    finite = bool(torch.isfinite(obs).all())
 
     if rank == 0:
         total_env_steps = world * n * args.steps
         value = total_env_steps / dt
-        achieved = ALGO_BYTES_PER_ENV_STEP * units_per_launch / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
-        # What the counters say about this kernel (rocprofv3 --pmc passes of the same workload, scripts/profile_round.sh; bench.py
-        # cannot profile itself).  HBM traffic feeds the contract's roofline object; the rest says what actually binds.
-        traffic, traffic_note, pmc = None, None, {}
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_latest.json")) as f:
-                pmc = json.load(f)
-            traffic = pmc["bytes_per_env_step"] * units_per_launch
-            traffic_note = ("builder-lease PMC, not this run: rocprofv3 --pmc FETCH_SIZE + WRITE_SIZE (separate passes, %s), %d B per env-step x %d env-steps per launch"
-                            % (pmc.get("source", "profiles/"), pmc["bytes_per_env_step"], units_per_launch))
-        except Exception:
-            pass
-        # chip-wide utilisation of THIS run: instructions per env-step (PMC, a property of the workload) x the measured env-step rate
-        # over the issue slots of the chip (SIMDs x clock; one wave-instruction per SIMD per cycle at best)
-        props = torch.cuda.get_device_properties(local)
-        simds, clk = props.multi_processor_count * 4, float(getattr(props, "clock_rate", 2.4e6)) * 1e3  # (kHz; MI355X_MICROARCH.md: 2.4 GHz peak engine clock)
-        per_gpu_rate = value / world
-        util = lambda k: (pmc[k] * per_gpu_rate / (simds * clk)) if pmc.get(k) else None
-        binding = {"bound": "per-wave instruction issue + LDS wait (not HBM, not MFMA); the step ends with its slowest env",
-                   "issue_util_this_run": util("insts_per_env_step"), "valu_util_this_run": util("valu_insts_per_env_step"),
-                   "util_def": "wave-instructions (all / VALU) issued per SIMD per cycle, chip-wide, over the timed region: PMC instructions per env-step x measured env-steps/s / (SIMDs x clock)",
-                   "simds": simds, "clock_hz": clk,
-                   "occupancy_this_run_waves_per_simd": (pmc["wave_cycles_per_env_step"] * per_gpu_rate / (simds * clk)) if pmc.get("wave_cycles_per_env_step") else None,
-                   "waves_per_simd_limit": 2,
-                   "wait_frac": pmc.get("wait_frac"), "issue_frac": pmc.get("issue_frac"),
-                   "insts_per_env_step": pmc.get("insts_per_env_step"), "valu_insts_per_env_step": pmc.get("valu_insts_per_env_step"),
-                   "wave_cycles_per_env_step": pmc.get("wave_cycles_per_env_step"),
-                   "algorithmic_flops_per_env_step": [1.5e6, 5.5e6], "fp32_vector_peak_tflops": 157.3,
-                   "achieved_tflops_algorithmic": [1.5e6 * per_gpu_rate / 1e12, 5.5e6 * per_gpu_rate / 1e12],
-                   "pmc_source": "builder-lease PMC passes (per-env-step counts), not this run: %s" % pmc.get("source"),
-                   # (builder-lease measurement of the benchmark's own slab 0, not this run: DESIGN.md section 6 item 6)
-                   "slab_of_1024_alone_vs_one_of_four": {"ms_per_step_alone": 4.15, "ms_per_step_one_of_four": 4.90, "env_slowdown_when_shared": 1.08,
-                                                         "launch_ends_with": "a second-round one-wave env that started ~1 ms late (31 of 35 steps)",
-                                                         "source": "profiles/r06_w_slab_alone_against_one_of_four.txt, profiles/r06_w_same_envs_alone_and_shared_timeline.txt"}}
         line = {
             "metric": "env-steps/sec (whole node), Sawyer+table_lack 4096 envs/GPU" if (args.agent, args.furniture, n, args.dense, args.control_type) == (AGENT, FURNITURE, ENVS_PER_GPU, False, "impedance")
             else "env-steps/sec (whole node), EXPLORATION %s+%s%s %d envs/GPU" % (args.agent, args.furniture, (" dense-reward" if args.dense else "") + ("" if args.control_type == "impedance" else " control_type=" + args.control_type), n), "value": value, "unit": "env-steps/s",
@@ -615,37 +616,80 @@ def main():
                        "resets_in_timed_region": la["swapped"] + la["inline"], "resets_taken_from_lookahead": la["swapped"], "resets_inside_step_launch": la["inline"],
                        "lookahead_reset_units_in_timed_region": la["units"],  # reset substeps run by look-ahead jobs (waves of the step launches that had no env left)
                        "reset_substeps_in_timed_region": la["units"] + la["inline"] * reset_substeps,
-                       "envs_that_dropped_contacts": dropped, "contact_slots": slabs[0].sim.max_contacts,
+                       "contact_slots": slabs[0].sim.max_contacts,
                        # env-steps (warm-up included) the library repeated with a 64-slot layout because 48 slots did not hold their contacts
                        # (fsim_overflow_resteps: done inside fsim_sync, i.e. inside the timed region)
                        "overflow_resteps": int(sum(sl.sim.overflow_resteps() for sl in slabs)),
-                       "episode_window": ew, "episode_window_env_steps_per_s": ew["env_steps_per_s"] if ew else None,
-                       "physics_substeps_per_s": value * 50, "obs_finite": finite, "obs_dtype": "bf16" if args.obs_bf16 else "f32", "kernel_variant": slabs[0].sim.kernel_variant,
+                       "physics_substeps_per_s": value * 50, "obs_dtype": "bf16" if args.obs_bf16 else "f32", "kernel_variant": slabs[0].sim.kernel_variant,
                        "reference_published_single_core_env_steps_per_s": 225},
+        }
+        if args.full:
+            # envs whose record carries the sticky contact-overflow word (fsim_model.hpp E_OVERFLOW): some launch since the handle was created
+            # -- warm-up included -- needed more contact slots than the kernel's LDS image holds and dropped the rest for that substep
+            from furniture_amd.sim import E_OVERFLOW
+            dropped = int(sum(int((sl.sim.get_state("env_block")["env_block"].view(torch.int32)[:, E_OVERFLOW] != 0).sum()) for sl in slabs))
+            finite = bool(torch.isfinite(torch.cat([sl.obs for sl in slabs])).all())
+            line["config"].update({"envs_that_dropped_contacts": dropped, "obs_finite": finite,
+                                   "episode_window": ew, "episode_window_env_steps_per_s": ew["env_steps_per_s"] if ew else None})
+            klaunches = sum(k[1] for k in kt)
+            kms = sum(k[0] * k[1] for k in kt) / max(1, klaunches)
+            achieved = ALGO_BYTES_PER_ENV_STEP * units_per_launch / (kms * 1e-3) / 1e9 if kms > 0 else 0.0
+            # What the counters say about this kernel (rocprofv3 --pmc passes of the same workload, scripts/profile_round.sh; bench.py
+            # cannot profile itself).  HBM traffic feeds the contract's roofline object; the rest says what actually binds.
+            traffic, traffic_note, pmc = None, None, {}
+            try:
+                with open(os.path.join(ROOT, "profiles", "pmc_latest.json")) as f:
+                    pmc = json.load(f)
+                traffic = pmc["bytes_per_env_step"] * units_per_launch
+                traffic_note = ("builder-lease PMC, not this run: rocprofv3 --pmc FETCH_SIZE + WRITE_SIZE (separate passes, %s), %d B per env-step x %d env-steps per launch"
+                                % (pmc.get("source", "profiles/"), pmc["bytes_per_env_step"], units_per_launch))
+            except Exception:
+                pass
+            # chip-wide utilisation of THIS run: instructions per env-step (PMC, a property of the workload) x the measured env-step rate
+            # over the issue slots of the chip (SIMDs x clock; one wave-instruction per SIMD per cycle at best)
+            props = torch.cuda.get_device_properties(local)
+            simds, clk = props.multi_processor_count * 4, float(getattr(props, "clock_rate", 2.4e6)) * 1e3  # (kHz; MI355X_MICROARCH.md: 2.4 GHz peak engine clock)
+            per_gpu_rate = value / world
+            util = lambda k: (pmc[k] * per_gpu_rate / (simds * clk)) if pmc.get(k) else None
+            binding = {"bound": "per-wave instruction issue + LDS wait (not HBM, not MFMA); the step ends with its slowest env",
+                       "issue_util_this_run": util("insts_per_env_step"), "valu_util_this_run": util("valu_insts_per_env_step"),
+                       "util_def": "wave-instructions (all / VALU) issued per SIMD per cycle, chip-wide, over the timed region: PMC instructions per env-step x measured env-steps/s / (SIMDs x clock)",
+                       "simds": simds, "clock_hz": clk,
+                       "occupancy_this_run_waves_per_simd": (pmc["wave_cycles_per_env_step"] * per_gpu_rate / (simds * clk)) if pmc.get("wave_cycles_per_env_step") else None,
+                       "waves_per_simd_limit": 2,
+                       "wait_frac": pmc.get("wait_frac"), "issue_frac": pmc.get("issue_frac"),
+                       "insts_per_env_step": pmc.get("insts_per_env_step"), "valu_insts_per_env_step": pmc.get("valu_insts_per_env_step"),
+                       "wave_cycles_per_env_step": pmc.get("wave_cycles_per_env_step"),
+                       "algorithmic_flops_per_env_step": [1.5e6, 5.5e6], "fp32_vector_peak_tflops": 157.3,
+                       "achieved_tflops_algorithmic": [1.5e6 * per_gpu_rate / 1e12, 5.5e6 * per_gpu_rate / 1e12],
+                       "pmc_source": "builder-lease PMC passes (per-env-step counts), not this run: %s" % pmc.get("source"),
+                       # (builder-lease measurement of the benchmark's own slab 0, not this run: DESIGN.md section 6 item 6)
+                       "slab_of_1024_alone_vs_one_of_four": {"ms_per_step_alone": 4.15, "ms_per_step_one_of_four": 4.90, "env_slowdown_when_shared": 1.08,
+                                                             "launch_ends_with": "a second-round one-wave env that started ~1 ms late (31 of 35 steps)",
+                                                             "source": "profiles/r06_w_slab_alone_against_one_of_four.txt, profiles/r06_w_same_envs_alone_and_shared_timeline.txt"}}
             # `bound`: what the contract's two choices are priced against is HBM (BASELINE.json asks for the HBM fraction) and `frac` is
             # computed against it; what actually binds is neither -- `bound_actual` / `binding` say what, with numbers.  `traffic` and the
             # per-env-step instruction counts come from the builder's own rocprofv3 PMC passes of this workload (profiles/pmc_latest.json),
             # the utilisation figures below are recomputed FOR THIS RUN from them and this run's measured rate.
-            "roofline": {"bound": "hbm", "bound_actual": "per-wave instruction issue + LDS latency, at a batch-synchronous step that ends with its slowest env (see binding)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
-                         "kernel": slabs[0].sim.step_kernel, "kernel_avg_ms": kms, "kernel_launches": klaunches,
-                         "algorithmic_bytes_per_launch": ALGO_BYTES_PER_ENV_STEP * units_per_launch,
-                         "env_steps_per_launch": units_per_launch,
-                         # `achieved` / `frac` price ONE launch (the contract's definition) -- but G launches of G slabs overlap on the chip, so the
-                         # chip-wide algorithmic rate over the timed region is the whole batch's bytes / the batched step's wall time
-                         "concurrent_launches": G, "chip_wide_achieved": ALGO_BYTES_PER_ENV_STEP * n / (dt / args.steps) / 1e9,
-                         "chip_wide_frac": ALGO_BYTES_PER_ENV_STEP * n / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
-                         "note": "fused 50-substep step keeps state in LDS: HBM fraction is ~0 by design; see `binding`",
-                         # what binds instead (SURVEY 8d asked for VALU utilisation and occupancy): one wavefront = one env, and a
-                         # wave issues at most one instruction per ~5 cycles (scripts/dev/micro: 5.0 cycles per dependent-distance-4
-                         # v_fma at 1-2 waves per SIMD), so an env-step costs ~5 cycles x instructions + LDS waits
-                         "binding": binding},
-        }
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.cpu_baseline)
-        else:  # (the contract times it on rank 0 at N = 1 only: the 1-GPU line of the same sweep carries it)
-            line["cpu_baseline"] = {"skipped": "--no-cpu-baseline" if args.no_cpu_baseline else "n_gpus > 1: timed at N = 1 only (see the 1-GPU line)"}
+            line["roofline"] = {"bound": "hbm", "bound_actual": "per-wave instruction issue + LDS latency, at a batch-synchronous step that ends with its slowest env (see binding)",
+                                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
+                                "kernel": slabs[0].sim.step_kernel, "kernel_avg_ms": kms, "kernel_launches": klaunches,
+                                "algorithmic_bytes_per_launch": ALGO_BYTES_PER_ENV_STEP * units_per_launch,
+                                "env_steps_per_launch": units_per_launch,
+                                # `achieved` / `frac` price ONE launch (the contract's definition) -- but G launches of G slabs overlap on the chip, so the
+                                # chip-wide algorithmic rate over the timed region is the whole batch's bytes / the batched step's wall time
+                                "concurrent_launches": G, "chip_wide_achieved": ALGO_BYTES_PER_ENV_STEP * n / (dt / args.steps) / 1e9,
+                                "chip_wide_frac": ALGO_BYTES_PER_ENV_STEP * n / (dt / args.steps) / 1e9 / HBM_PEAK_GBS,
+                                "note": "fused 50-substep step keeps state in LDS: HBM fraction is ~0 by design; see `binding`",
+                                # what binds instead (SURVEY 8d asked for VALU utilisation and occupancy): one wavefront = one env, and a
+                                # wave issues at most one instruction per ~5 cycles (scripts/dev/micro: 5.0 cycles per dependent-distance-4
+                                # v_fma at 1-2 waves per SIMD), so an env-step costs ~5 cycles x instructions + LDS waits
+                                "binding": binding}
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.cpu_baseline)
+            else:  # (the contract times it on rank 0 at N = 1 only: the 1-GPU line of the same sweep carries it)
+                line["cpu_baseline"] = {"skipped": "--no-cpu-baseline" if args.no_cpu_baseline else "n_gpus > 1: timed at N = 1 only (see the 1-GPU line)"}
         print(json.dumps(line))
     for sl in slabs:
         sl.tables.close()

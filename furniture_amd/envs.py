@@ -101,12 +101,18 @@ def _host_lib():
 
 def host_threads():
     """OpenMP threads one call of libfsim_host.so may use: this rank's share of the host cores.  The ranks of one node reach their
-    batch-wide reset on the same step; uncapped, each of 8 ranks would start one thread per core for the same 14 ms."""
+    batch-wide reset on the same step; uncapped, each of 8 ranks would start one thread per core for the same 14 ms.  OMP_NUM_THREADS, when
+    set, caps it: a process held to fewer cores than the machine has (a CPU quota) is throttled once its threads have used them up -- 256
+    threads under a 16-core quota took 100-200 ms per 4096-env draw instead of ~10."""
     import os
     if os.environ.get("FSIM_HOST_THREADS"):
         return max(1, int(os.environ["FSIM_HOST_THREADS"]))
     ranks = int(os.environ.get("LOCAL_WORLD_SIZE") or os.environ.get("WORLD_SIZE") or 1)
-    return max(1, (os.cpu_count() or 1) // max(1, ranks))
+    cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    n = cores // max(1, ranks)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():  # (a per-process budget already)
+        n = min(n, int(os.environ["OMP_NUM_THREADS"]))
+    return max(1, n)
 
 
 class ResetTableSampler:

@@ -4,7 +4,7 @@ O=gpurun_out/$1; mkdir -p $O; shift
 for rep in 1 2; do
 for tag in "$@"; do
   lib=furniture_amd/csrc/libfsim_$tag.so; [ "$tag" = base ] && lib=furniture_amd/csrc/libfsim.so
-  FSIM_LIB=$PWD/$lib timeout 200 python bench.py --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err
+  FSIM_LIB=$PWD/$lib timeout 200 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err
   python - $O/bench_${tag}_$rep.json $tag <<'PY'
 import json,sys
 try:

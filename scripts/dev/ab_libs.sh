@@ -7,7 +7,7 @@ for tag in "$@"; do
   FSIM_LIB=$PWD/$prof timeout 200 python scripts/gpu_phase_profile.py 7 > $O/phase_$tag.log 2>&1
   echo "== $tag"; grep -E "^step  [05]|per-substep kcycles \(median|SLOW env [0-9]+: Mcyc" $O/phase_$tag.log | cut -c1-460
   for rep in 1 2; do
-    FSIM_LIB=$PWD/$lib timeout 200 python bench.py --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err
+    FSIM_LIB=$PWD/$lib timeout 200 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err
     python - $O/bench_${tag}_$rep.json $tag <<'PY'
 import json,sys
 try:

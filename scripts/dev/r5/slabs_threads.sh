@@ -2,7 +2,7 @@ export PYTHONPATH=$PWD
 O=gpurun_out/r5b; mkdir -p $O
 run() { # tag env... -- args
   tag=$1; shift
-  env "$@" timeout 200 python bench.py --steps 60 --warmup 5 --no-cpu-baseline $ARGS > $O/$tag.json 2> $O/$tag.err
+  env "$@" timeout 200 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline $ARGS > $O/$tag.json 2> $O/$tag.err
   python - $O/$tag.json $tag <<'PY'
 import json,sys
 try:

@@ -11,16 +11,16 @@ for l in open('$1'):
 "; }
 export FSIM_HANDOVER_STATS=1
 for rep in 1 2; do
-  FSIM_LIB=$R/furniture_amd/csrc/libfsim.so timeout 120 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_base_$rep.json 2> $O/w100_base_$rep.err || echo "rc $?"
+  FSIM_LIB=$R/furniture_amd/csrc/libfsim.so timeout 120 python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_base_$rep.json 2> $O/w100_base_$rep.err || echo "rc $?"
   line $O/w100_base_$rep.json "shipped, 100 steps"
-  FSIM_LIB=$LIBHO FSIM_NO_HANDOVER=1 timeout 120 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_off_$rep.json 2> $O/w100_off_$rep.err || echo "rc $?"
+  FSIM_LIB=$LIBHO FSIM_NO_HANDOVER=1 timeout 120 python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_off_$rep.json 2> $O/w100_off_$rep.err || echo "rc $?"
   line $O/w100_off_$rep.json "variant, hand-over off, 100 steps"
-  FSIM_LIB=$LIBHO timeout 120 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_on_$rep.json 2> $O/w100_on_$rep.err || echo "rc $?"
+  FSIM_LIB=$LIBHO timeout 120 python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_on_$rep.json 2> $O/w100_on_$rep.err || echo "rc $?"
   line $O/w100_on_$rep.json "variant, hand-over on, 100 steps"; grep 'handed over' $O/w100_on_$rep.err | head -4
 done
 for tag in base on; do
   lib=$LIBHO; [ $tag = base ] && lib=$R/furniture_amd/csrc/libfsim.so
-  FSIM_LIB=$lib timeout 120 python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/drv_${tag}.json 2> $O/drv_${tag}.err || echo "rc $?"
+  FSIM_LIB=$lib timeout 120 python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/drv_${tag}.json 2> $O/drv_${tag}.err || echo "rc $?"
   line $O/drv_${tag}.json "$tag, driver command"
 done
 if [ -n "$1" ]; then

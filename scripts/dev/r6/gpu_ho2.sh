@@ -14,7 +14,7 @@ export FSIM_HANDOVER_STATS=1
 for it in ${IT_LIST:-off 36 30 24 18 off 30}; do
   for rep in 1 2; do
     if [ $it = off ]; then export FSIM_NO_HANDOVER=1; else unset FSIM_NO_HANDOVER; export FSIM_HANDOVER_ITERS=$it; fi
-    timeout 120 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_${it}_$rep.json 2> $O/w100_${it}_$rep.err || echo "rc $?"
+    timeout 120 python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_${it}_$rep.json 2> $O/w100_${it}_$rep.err || echo "rc $?"
     line $O/w100_${it}_$rep.json "threshold $it, 100 steps"; grep 'handed over' $O/w100_${it}_$rep.err | head -1 | cut -c20-120
   done
 done

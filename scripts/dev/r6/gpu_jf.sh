@@ -12,13 +12,13 @@ for l in open('$1'):
 for rep in 1 2 3; do
   for tag in base $TAG; do
     lib=$R/furniture_amd/csrc/libfsim_$tag.so; [ $tag = base ] && lib=$R/furniture_amd/csrc/libfsim.so
-    FSIM_LIB=$lib timeout 120 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_${tag}_$rep.json 2> $O/w100_${tag}_$rep.err || echo "rc $?"
+    FSIM_LIB=$lib timeout 120 python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_${tag}_$rep.json 2> $O/w100_${tag}_$rep.err || echo "rc $?"
     line $O/w100_${tag}_$rep.json "$tag, 100 steps"
   done
 done
 for tag in base $TAG base $TAG; do
   lib=$R/furniture_amd/csrc/libfsim_$tag.so; [ $tag = base ] && lib=$R/furniture_amd/csrc/libfsim.so
-  FSIM_LIB=$lib timeout 120 python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/drv_${tag}.json 2> $O/drv_${tag}.err || echo "rc $?"
+  FSIM_LIB=$lib timeout 120 python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/drv_${tag}.json 2> $O/drv_${tag}.err || echo "rc $?"
   line $O/drv_${tag}.json "$tag, driver command"
 done
 if [ -n "$2" ]; then

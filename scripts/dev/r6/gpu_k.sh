@@ -13,6 +13,6 @@ done
 cd $R
 for rep in 1 2 3; do for tag in base warm; do
   lib=$R/furniture_amd/csrc/libfsim.so; [ $tag = warm ] && lib=$R/furniture_amd/csrc/libfsim_warm.so
-  FSIM_LIB=$lib python bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err
+  FSIM_LIB=$lib python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/bench_${tag}_$rep.json 2> $O/bench_${tag}_$rep.err
   echo BENCH $tag $rep $(python -c "import json; d=json.load(open('$O/bench_${tag}_$rep.json')); print(round(d['value']), round(d['ms_per_step'],3), round(d['roofline']['kernel_avg_ms'],3))")
 done; done

@@ -10,7 +10,7 @@ for l in open('$1'):
 "; }
 for sp in ${SP_LIST:-0 0.3 0.6 0.9 1.2 0}; do
   for rep in 1 2; do
-    FSIM_BENCH_SPACING_MS=$sp timeout 120 python $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w200_s${sp}_$rep.json 2> $O/w200_s${sp}_$rep.err || echo "rc $?"
+    FSIM_BENCH_SPACING_MS=$sp timeout 120 python $R/bench.py --full --steps 200 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w200_s${sp}_$rep.json 2> $O/w200_s${sp}_$rep.err || echo "rc $?"
     line $O/w200_s${sp}_$rep.json "spacing $sp ms, 200 steps"
   done
 done

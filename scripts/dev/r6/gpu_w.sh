@@ -5,7 +5,7 @@
 #   b) how busy the CU's one LDS unit is: SQ_LDS_IDX_ACTIVE / SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS / SQ_WAIT_INST_LDS against the kernel's cycles
 R=$PWD; O=$R/gpurun_out/r6w; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0"
+B="python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0"
 line() { python -c "
 import json,sys
 for l in open('$1'):

@@ -7,7 +7,7 @@ ls /sys/class/drm/ > $O/drm.txt 2>&1
 SCLK=$(ls /sys/class/drm/card*/device/pp_dpm_sclk 2>/dev/null | head -1)
 echo "sclk file: $SCLK"; cat $SCLK 2>&1 | head -5
 watch_clk() { while true; do grep '\*' $SCLK 2>/dev/null | tr '\n' ' '; rocm-smi --showpower 2>/dev/null | grep -i 'power' | head -1 | tr -s ' ' | cut -c1-90; sleep 1.0; done; }
-B="python $R/bench.py --steps 2000 --warmup 10 --no-cpu-baseline --episode-window 0"
+B="python $R/bench.py --full --steps 2000 --warmup 10 --no-cpu-baseline --episode-window 0"
 for mode in "solo --envs-per-gpu 1024 --groups 1" "four"; do
   set -- $mode; tag=$1; shift
   watch_clk > $O/clk_$tag.txt & W=$!

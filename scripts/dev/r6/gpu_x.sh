@@ -12,9 +12,9 @@ for l in open('$1'):
 "; }
 for rsv in ${RSV_LIST:-0 1 2 3 0 2}; do
   for rep in 1 2; do
-    FSIM_RESERVE=$rsv timeout 120 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_r${rsv}_$rep.json 2> $O/w100_r${rsv}_$rep.err || echo "rc $? (reserve $rsv)"
+    FSIM_RESERVE=$rsv timeout 120 python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_r${rsv}_$rep.json 2> $O/w100_r${rsv}_$rep.err || echo "rc $? (reserve $rsv)"
     line $O/w100_r${rsv}_$rep.json "reserve $rsv, 100 steps"
   done
-  FSIM_RESERVE=$rsv timeout 120 python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/drv_r${rsv}.json 2> $O/drv_r${rsv}.err || echo "rc $? (reserve $rsv)"
+  FSIM_RESERVE=$rsv timeout 120 python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/drv_r${rsv}.json 2> $O/drv_r${rsv}.err || echo "rc $? (reserve $rsv)"
   line $O/drv_r${rsv}.json "reserve $rsv, driver command"
 done

@@ -11,9 +11,9 @@ for l in open('$1'):
 "; }
 for n in ${PRIO_LIST:-0 16 32 64 0 32}; do
   for rep in 1 2; do
-    FSIM_LONG_PRIO=$n timeout 120 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_p${n}_$rep.json 2> $O/w100_p${n}_$rep.err || echo "rc $? (prio $n)"
+    FSIM_LONG_PRIO=$n timeout 120 python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_p${n}_$rep.json 2> $O/w100_p${n}_$rep.err || echo "rc $? (prio $n)"
     line $O/w100_p${n}_$rep.json "high-priority workgroups $n, 100 steps"
   done
-  FSIM_LONG_PRIO=$n timeout 120 python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/drv_p${n}.json 2> $O/drv_p${n}.err || echo "rc $? (prio $n)"
+  FSIM_LONG_PRIO=$n timeout 120 python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/drv_p${n}.json 2> $O/drv_p${n}.err || echo "rc $? (prio $n)"
   line $O/drv_p${n}.json "high-priority workgroups $n, driver command"
 done

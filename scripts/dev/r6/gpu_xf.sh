@@ -19,7 +19,7 @@ for l in open('$1'):
 "; }
 for xf in 0 4 8 16 0 8; do
   for rep in 1 2; do
-    FSIM_X_FIRST=$xf timeout 120 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_x${xf}_$rep.json 2> $O/w100_x${xf}_$rep.err || echo "rc $?"
+    FSIM_X_FIRST=$xf timeout 120 python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --episode-window 0 > $O/w100_x${xf}_$rep.json 2> $O/w100_x${xf}_$rep.err || echo "rc $?"
     line $O/w100_x${xf}_$rep.json "bundle-first workgroups $xf, 100 steps"
   done
 done
