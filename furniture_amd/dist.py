@@ -75,7 +75,10 @@ def step_wait_and_gather(sim, obs, reward, done, tag=0, stream=None, group=None)
     re-step an env whose contacts did not fit the kernel's slots and rewrite its rows (include/fsim.h fsim_overflow_resteps) --, THEN the
     all-gather, so that every rank receives the rows that are final.  A gather enqueued behind the step kernel instead would carry the
     first pass's rows of such an env, and repeating it only on the rank that saw the re-step is not possible (a collective is entered by
-    every rank).  One collective per slab-step on every rank, whatever happened.  ``sim``: anything with ``sync()`` (furniture_amd.sim.FSim)."""
+    every rank).  One collective per slab-step on every rank, whatever happened.  ``sim``: anything with ``sync()`` (furniture_amd.sim.FSim).
+    Camera images are not gathered: a handle with cameras set is refused."""
+    if getattr(sim, "cameras", None):
+        raise NotImplementedError("step_wait_and_gather: camera images are not part of the multi-GPU gather; render on each rank instead")
     sim.sync()
     out = gather_observations(obs, reward, done, tag=tag, stream=stream, group=group)
     if stream is not None and obs.is_cuda:

@@ -355,10 +355,15 @@ _AGENT_OF = {"FurnitureSawyerEnv": "Sawyer", "FurnitureBaxterEnv": "Baxter", "Fu
 class FurnitureBatchEnv:
     """n_envs copies of FurnitureEnv on one GPU.  Observations / rewards / dones are torch tensors on the device."""
 
-    def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False, **kw):
+    cameras = None
+
+    def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
+                 cameras=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
-        obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32."""
+        obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
+        cameras: a list of furniture_amd.camera.Camera -- reset() / step() then add camera_depth (float32) and camera_segmentation
+        (int32, model geom ids), [n, C, H, W] device tensors rendered from the collision geometry after the step's sync."""
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -375,7 +380,8 @@ class FurnitureBatchEnv:
                           stacklevel=3)
             cfg.unity, cfg.record_vid = False, False
         if cfg.visual_ob:
-            raise ValueError("visual_ob must be False: camera observations need the renderer, which is outside the accelerated hot path")
+            raise ValueError("visual_ob must be False: RGB camera observations need the reference's visual meshes and renderer, which are "
+                             "outside the accelerated hot path (depth / segmentation of the collision geometry: cameras=[Camera(...)])")
         # "torque" (furniture.py:1268): _do_simulation(action[:-1]) = the impedance flow -- _setup_action turns [7 arm, 1 grip] into the 9
         # actuator controls and rescales them to the ctrlrange -- on the motor-actuated robot (robot_torque.xml): same kernel, other model
         if agent != "Cursor" and cfg.control_type not in ("impedance", "torque") and cfg.control_type not in CONTROLLER_CODES:
@@ -456,6 +462,11 @@ class FurnitureBatchEnv:
         self._auto_reset = bool(auto_reset)
         self.n_obj = self.model.nparts
         self.refill_tables_every_step = True
+        self.cameras = list(cameras) if cameras else None
+        if self.cameras:  # (without cameras: no allocation, no launch, the same observation dict)
+            self.sim.set_cameras(self.cameras)
+            shape = (num_envs, len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+            self._cam_out = (torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.int32, device=dev))
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -475,7 +486,24 @@ class FurnitureBatchEnv:
             sp.append(("robot_ob", spaces.Box(-np.inf, np.inf, shape=(self.sim.obs_dim - 7 * self.n_obj,))))
         if self.dense and getattr(cfg, "phase_ob", False):  # furniture_sawyer_dense.py:98-108
             sp.append(("phase_ob", spaces.Box(0.0, 1.0, shape=(8,))))
+        if self.cameras:
+            shape = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+            sp.append(("camera_depth", spaces.Box(0.0, max(c.zfar for c in self.cameras), shape=shape, dtype=np.float32)))
+            sp.append(("camera_segmentation", spaces.Box(-1, self.model.ngeom - 1, shape=shape, dtype=np.int32)))
         return spaces.Dict(sp)
+
+    def geom_labels(self):
+        """[ngeom] int32 device tensor: part index of every furniture geom, -2 robot, -3 floor / arena (furniture_amd.camera.geom_labels):
+        part masks of camera_segmentation with one gather."""
+        from .camera import geom_labels
+        return self.sim.torch.as_tensor(geom_labels(self.model), device=self.sim.device)
+
+    def _observe(self, subtask=None):
+        """the observation dict of the state the last sync() left: _split of the slab, plus the camera images when cameras are set"""
+        out = self._split(self._obs, subtask)
+        if self.cameras:
+            out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
+        return out
 
     @property
     def action_space(self):
@@ -620,14 +648,14 @@ class FurnitureBatchEnv:
             if not hasattr(self, "_attach_after_reset"):
                 self._attach_after_reset, self._attach_after_attach = [None] * self.num_envs, [None] * self.num_envs
             self._attach_reset(np.ones(self.num_envs, dtype=bool))
-            return self._split(self._obs)
+            return self._observe()
         if getattr(self, "_init_qpos", None) is not None:
             if not self._tables_fresh.all():  # (the kernel insists on tables being present; these are not consumed)
                 self._refill(None if not self._tables_fresh.any() else ~self._tables_fresh)
             self.sim.reset(None, self._obs)
             self.sim.sync()
             self._check_overflow_after_reset()
-            return self._split(self._obs)
+            return self._observe()
         # one table = one pass of the reference's reset-time RNG stream: a table that is on the device but was never
         # consumed (uploaded for an auto-reset that did not happen yet) IS the next draw of that env and is used as is
         stale = ~self._tables_fresh
@@ -640,7 +668,7 @@ class FurnitureBatchEnv:
         # the next draw of every env's stream goes to the device now: the in-kernel resets read it (the auto-reset of a terminal
         # step; without auto_reset, the reset an unstable simulation triggers inside step(), furniture.py:2889-2897)
         self._refill(lookahead=True)
-        return self._split(self._obs)
+        return self._observe()
 
     def rng_handover(self):
         """The per-env RandomState objects positioned at the first draw no reset has consumed yet (tables drawn ahead -- one in
@@ -698,7 +726,7 @@ class FurnitureBatchEnv:
         else:  # the reward terms _compute_reward reports (furniture.py:535-540); float bits in the int32 info block
             fl = info[:, INFO_SUCCESS_REWARD_F:INFO_CTRL_PENALTY_F + 1].view(self.sim.torch.float32)
             infos.update(success_reward=fl[:, 0], touch_reward=fl[:, 1], pick_reward=fl[:, 2], ctrl_penalty=fl[:, 3])
-        return self._split(self._obs, info[:, INFO_SUBTASK1:INFO_SUBTASK1 + 2]), self._rew, self._done.bool(), infos
+        return self._observe(info[:, INFO_SUBTASK1:INFO_SUBTASK1 + 2]), self._rew, self._done.bool(), infos
 
     def step(self, actions):
         self.step_async(actions)
@@ -808,7 +836,7 @@ class _SingleEnv:
             rngs = old.rng_handover()
             dev = old.sim.device.index or 0
             old.close()
-            self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense)
+            self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())
@@ -827,7 +855,17 @@ class _SingleEnv:
         return {k: v[0].cpu().numpy() for k, v in s.items()}
 
     def render(self, mode="human"):
-        raise NotImplementedError("rendering (Unity / MuJoCo viewer) is outside the accelerated hot path")
+        """"depth_array": the depth image [H, W] (metres) of camera 0 of the current state (needs cameras=[...]).  RGB ("rgb_array",
+        "human") is not available: the compiled models hold no visual meshes, only the collision geometry the cameras see."""
+        if mode != "depth_array":
+            raise NotImplementedError("render(%r): RGB rendering needs the reference's visual meshes (not part of the compiled model) and "
+                                      "the Unity / MuJoCo viewer, both outside the accelerated hot path; render('depth_array') gives the "
+                                      "depth image of the collision geometry (cameras=[Camera(...)])" % mode)
+        if not self._b.cameras:
+            raise ValueError("render('depth_array') needs cameras: make the env with cameras=[furniture_amd.camera.Camera(...)]")
+        self._b.sim.sync()
+        depth, _ = self._b.sim.render(segmentation=False)
+        return depth[0, 0].cpu().numpy()
 
     def close(self):
         self._b.close()

@@ -37,6 +37,10 @@ class FurnitureMixedBatchEnv:
     """VecEnv-shaped like FurnitureBatchEnv, over several furniture models of one agent."""
 
     def __init__(self, agent, furniture_names, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, **kw):
+        if kw.get("cameras"):
+            raise NotImplementedError("cameras= is not supported by the mixed-furniture batch (one camera set per FurnitureBatchEnv): "
+                                      "make one FurnitureBatchEnv per furniture instead")
+        kw.pop("cameras", None)
         cfg = config if config is not None else make_config()
         for key, v in kw.items():
             setattr(cfg, key, v)

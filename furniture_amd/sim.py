@@ -62,7 +62,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs.append(os.path.join(os.path.dirname(_HERE), "include", "fsim.h"))
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -159,6 +159,8 @@ def lib():
         L.fsim_set_preassembled.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.fsim_dense_replay.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + \
             [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.fsim_set_cameras.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fsim_render.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _LIB = L
     return _LIB
 
@@ -172,6 +174,8 @@ EXPORTED_SYMBOLS = [
     "fsim_replay_is_aligned", "fsim_replay_try_connect", "fsim_replay_touch_scan", "fsim_set_init_state", "fsim_tables_needed", "fsim_set_preassembled", "fsim_set_attach_noise",
     "fsim_read",
 ]
+# the camera entry points: a header of their own (include/fsim_camera.h), exported by the same library
+CAMERA_SYMBOLS = ["fsim_set_cameras", "fsim_render"]
 
 
 def preassembled_rows(model, preassembled):
@@ -428,6 +432,43 @@ class FSim:
         masks, tried = np.zeros((n, 3), dtype=np.int32), np.zeros((n, 4), dtype=np.int32)
         self._chk(lib().fsim_replay_touch_scan(self._h, n, maxc, ncon.ctypes.data, geoms.ctypes.data, sc.ctypes.data, masks.ctypes.data, tried.ctypes.data))
         return masks, tried
+
+    # -- depth / segmentation cameras (include/fsim_camera.h, furniture_amd/camera.py) --------------------------------------
+    cameras = None
+
+    def set_cameras(self, cams):
+        """Replace the handle's camera set (a list of furniture_amd.camera.Camera); validated by the library."""
+        from .camera import camera_table, hull_plane_table
+        cams = list(cams)
+        tab = camera_table(self.cm, cams)
+        planes, adr, num = hull_plane_table(self.cm)
+        self._chk(lib().fsim_set_cameras(self._h, len(cams), tab.ctypes.data, len(planes), planes.ctypes.data if len(planes) else None,
+                                         adr.ctypes.data, num.ctypes.data))
+        self.cameras = cams
+
+    def render(self, depth=True, segmentation=True, out=None):
+        """Depth (float32, metres along the optical axis) and segmentation (int32 model geom id, -1 = nothing) images of every env from
+        every camera, [n_envs, n_cam, H, W] device tensors (None for the one not asked for) of the state sync() leaves.  out: a
+        (depth, segmentation) pair of tensors to render into instead of new ones.  Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if not self.cameras:
+            raise FsimError("render: no cameras set (FSim.set_cameras)")
+        if not (depth or segmentation):
+            raise ValueError("render: neither depth nor segmentation asked for")
+        shape = (self.n_envs, len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+        d, s = out if out is not None else (None, None)
+        if depth and d is None:
+            d = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if segmentation and s is None:
+            s = torch.empty(shape, dtype=torch.int32, device=self.device)
+        d, s = (d if depth else None), (s if segmentation else None)
+        for t, dt in ((d, torch.float32), (s, torch.int32)):
+            assert t is None or (tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous()), "render: out tensor of the wrong shape / type"
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_render(self._h, d.data_ptr() if d is not None else None, s.data_ptr() if s is not None else None))
+        cur.wait_stream(self.torch_stream)
+        return d, s
 
     def kernel_time_ms(self):
         ms, n = ctypes.c_double(), ctypes.c_int32()

@@ -42,6 +42,9 @@ class FurnitureVecEnv:
             raise Exception("unknown env id %s" % env_id)
         kw = dict(defaults)
         kw.update(env_kwargs or {})
+        if kw.pop("cameras", None):
+            raise NotImplementedError("cameras= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., cameras=[...]), whose images stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
@@ -97,7 +100,8 @@ class FurnitureVecEnv:
         return self.step_wait()
 
     def get_images(self):
-        raise NotImplementedError("rendering (Unity / MuJoCo viewer) is outside the accelerated hot path")
+        raise NotImplementedError("get_images: RGB rendering (Unity / MuJoCo viewer, visual meshes) is outside the accelerated hot path; "
+                                  "depth / segmentation cameras of the collision geometry: FurnitureBatchEnv(..., cameras=[...])")
 
     def render(self, mode="human"):
         return self.get_images()
