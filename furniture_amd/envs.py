@@ -356,14 +356,21 @@ class FurnitureBatchEnv:
     """n_envs copies of FurnitureEnv on one GPU.  Observations / rewards / dones are torch tensors on the device."""
 
     cameras = None
+    point_cloud = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, **kw):
+                 cameras=None, point_cloud=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
         cameras: a list of furniture_amd.camera.Camera -- reset() / step() then add camera_depth (float32) and camera_segmentation
-        (int32, model geom ids), [n, C, H, W] device tensors rendered from the collision geometry after the step's sync."""
+        (int32, model geom ids), [n, C, H, W] device tensors rendered from the collision geometry after the step's sync.
+        point_cloud: a furniture_amd.points.PointCloud (needs cameras) -- the observations then also hold point_cloud (float32 world
+        xyz, [n, N, 3]; dense mode [n, C, H, W, 3]), point_cloud_segmentation (int32 model geom id, -1 = padding) and point_cloud_count
+        (int32 [n], the kept pixels), built from the same render as the images."""
+        if point_cloud is not None:
+            from .points import check
+            check(point_cloud, list(cameras) if cameras else None)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -467,6 +474,12 @@ class FurnitureBatchEnv:
             self.sim.set_cameras(self.cameras)
             shape = (num_envs, len(self.cameras), self.cameras[0].height, self.cameras[0].width)
             self._cam_out = (torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.int32, device=dev))
+        self.point_cloud = point_cloud
+        if point_cloud is not None:  # (without it: no allocation, no launch, the same observation dict)
+            self.sim.set_points(point_cloud)
+            self._pts_out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
+            for k, (sh, dt) in self.sim.points_shapes().items():
+                self._pts_out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -490,6 +503,11 @@ class FurnitureBatchEnv:
             shape = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
             sp.append(("camera_depth", spaces.Box(0.0, max(c.zfar for c in self.cameras), shape=shape, dtype=np.float32)))
             sp.append(("camera_segmentation", spaces.Box(-1, self.model.ngeom - 1, shape=shape, dtype=np.int32)))
+        if self.point_cloud is not None:
+            per = shape if self.point_cloud.dense else (self.point_cloud.n_points,)
+            sp.append(("point_cloud", spaces.Box(-np.inf, np.inf, shape=per + (3,), dtype=np.float32)))
+            sp.append(("point_cloud_segmentation", spaces.Box(-1, self.model.ngeom - 1, shape=per, dtype=np.int32)))
+            sp.append(("point_cloud_count", spaces.Box(0, int(np.prod(shape)), shape=(), dtype=np.int32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -499,9 +517,14 @@ class FurnitureBatchEnv:
         return self.sim.torch.as_tensor(geom_labels(self.model), device=self.sim.device)
 
     def _observe(self, subtask=None):
-        """the observation dict of the state the last sync() left: _split of the slab, plus the camera images when cameras are set"""
+        """the observation dict of the state the last sync() left: _split of the slab, plus the camera images when cameras are set and
+        the point cloud when one is set (images and points from one fsim_render_points call: one ray pass)"""
         out = self._split(self._obs, subtask)
-        if self.cameras:
+        if self.point_cloud is not None:
+            res = self.sim.render_points(images=True, out=self._pts_out)
+            for k in ("camera_depth", "camera_segmentation", "point_cloud", "point_cloud_segmentation", "point_cloud_count"):
+                out[k] = res[k]
+        elif self.cameras:
             out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
         return out
 
@@ -836,7 +859,8 @@ class _SingleEnv:
             rngs = old.rng_handover()
             dev = old.sim.device.index or 0
             old.close()
-            self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras)
+            self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
+                                         point_cloud=old.point_cloud)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

@@ -62,7 +62,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -161,6 +161,8 @@ def lib():
             [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.fsim_set_cameras.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fsim_render.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fsim_set_points.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.fsim_render_points.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6
         _LIB = L
     return _LIB
 
@@ -176,6 +178,8 @@ EXPORTED_SYMBOLS = [
 ]
 # the camera entry points: a header of their own (include/fsim_camera.h), exported by the same library
 CAMERA_SYMBOLS = ["fsim_set_cameras", "fsim_render"]
+# the point-cloud entry points: a header of their own (include/fsim_points.h), exported by the same library
+POINTS_SYMBOLS = ["fsim_set_points", "fsim_render_points"]
 
 
 def preassembled_rows(model, preassembled):
@@ -469,6 +473,60 @@ class FSim:
         self._chk(lib().fsim_render(self._h, d.data_ptr() if d is not None else None, s.data_ptr() if s is not None else None))
         cur.wait_stream(self.torch_stream)
         return d, s
+
+    # -- point clouds from the cameras (include/fsim_points.h, furniture_amd/points.py) ------------------------------------------
+    points = None
+
+    def set_points(self, spec):
+        """Set the point-cloud settings (a furniture_amd.points.PointCloud); checked on the host first, then by the library."""
+        from .points import PointCloud, geom_keep
+        if not isinstance(spec, PointCloud):
+            raise TypeError("set_points: a furniture_amd.points.PointCloud, not %r" % type(spec).__name__)
+        keep = np.ascontiguousarray(geom_keep(self.cm, spec.include), dtype=np.uint8)
+        box = None if spec.box is None else np.ascontiguousarray(spec.box, dtype=np.float32).reshape(6)
+        self._chk(lib().fsim_set_points(self._h, spec.n_points, keep.ctypes.data, None if box is None else box.ctypes.data))
+        self.points = spec
+
+    def points_shapes(self):
+        """{key: (shape, dtype)} of render_points' outputs (without the n_envs dimension); dense mode has no point_cloud_pixel"""
+        torch = self.torch
+        C, H, W = len(self.cameras), self.cameras[0].height, self.cameras[0].width
+        n = self.points.n_points
+        per = (C, H, W) if n == 0 else (n,)
+        out = {"point_cloud": (per + (3,), torch.float32), "point_cloud_segmentation": (per, torch.int32), "point_cloud_count": ((), torch.int32)}
+        if n > 0:
+            out["point_cloud_pixel"] = ((n,), torch.int32)
+        return out
+
+    def render_points(self, images=False, out=None):
+        """Render the cameras once and turn the images into points (include/fsim_points.h), for the state sync() leaves -> dict of device
+        tensors: point_cloud (float32 world xyz), point_cloud_segmentation (int32 model geom id, -1 = none), point_cloud_count (int32 [n]:
+        the kept pixels), in sampled mode point_cloud_pixel (int32 cam*H*W + row*W + col, -1 = none), and with images=True camera_depth /
+        camera_segmentation [n, C, H, W] as FSim.render gives them.  out: a dict of such tensors to write into instead of new ones.
+        Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if self.points is None:
+            raise FsimError("render_points: no point-cloud settings (FSim.set_points)")
+        if not self.cameras:
+            raise FsimError("render_points: no cameras set (FSim.set_cameras)")
+        want = self.points_shapes()
+        if images:
+            img = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+            want["camera_depth"], want["camera_segmentation"] = (img, torch.float32), (img, torch.int32)
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "render_points: out[%r] of the wrong shape / type" % k
+            res[k] = t
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_render_points(self._h, ptr("camera_depth"), ptr("camera_segmentation"), ptr("point_cloud"),
+                                           ptr("point_cloud_segmentation"), ptr("point_cloud_pixel"), ptr("point_cloud_count")))
+        cur.wait_stream(self.torch_stream)
+        return res
 
     def kernel_time_ms(self):
         ms, n = ctypes.c_double(), ctypes.c_int32()

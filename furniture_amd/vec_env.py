@@ -45,6 +45,9 @@ class FurnitureVecEnv:
         if kw.pop("cameras", None):
             raise NotImplementedError("cameras= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., cameras=[...]), whose images stay on the device")
+        if kw.pop("point_cloud", None) is not None:
+            raise NotImplementedError("point_cloud= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., cameras=[...], point_cloud=PointCloud(...)), whose points stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
