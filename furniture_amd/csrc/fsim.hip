@@ -507,6 +507,7 @@ typedef void (*EnvStepXFn)(const DModel *, const Layout *, const Layout *, KPara
 #define FSIM_OVF_CAP 1024    // envs of one step launch the overflow re-step lists, at most (the others keep their sticky report)
 struct CamState; // fsim_camera.hpp
 struct PtsState; // fsim_points.hpp
+struct VoxState; // fsim_voxels.hpp
 struct KernelSet { const char *name; PhysicsFn physics; EnvStepFn env_step; PhysicsFn physics_mw; EnvStepFn env_step_mw; EnvStepXFn env_step_x; };
 enum { MW_OFF = 0, MW_RULE = 1, MW_ALL = 2 }; // fsim::mw_mode
 
@@ -586,6 +587,7 @@ struct fsim {
   int la_jobs = 0, la_defer = 0, la_chunk = 0; // jobs per launch, steps into the episode before an env's shadow is started, reset units per job
   CamState *cam = nullptr; // depth / segmentation cameras (fsim_set_cameras): nothing is allocated or launched without them
   PtsState *pts = nullptr; // point-cloud settings and scratch (fsim_set_points): nothing is allocated or launched without them
+  VoxState *vox = nullptr; // voxel-grid settings and scratch (fsim_set_voxels): nothing is allocated or launched without them
 };
 
 static void la_policy(fsim *s);
@@ -998,12 +1000,14 @@ extern "C" int fsim_create(const void *model_blob, size_t nbytes, int n_envs, in
 
 static void cam_free(fsim *s);
 static void pts_free(fsim *s);
+static void vox_free(fsim *s);
 extern "C" void fsim_destroy(fsim_t *s) {
   if (!s) return;
   hipSetDevice(s->device);
   if (s->stream) hipStreamSynchronize(s->stream);
   cam_free(s);
   pts_free(s);
+  vox_free(s);
   hipFree(s->d_sh_state); hipFree(s->d_sh_obs); hipFree(s->d_sh_prog); hipFree(s->d_sh_serial); hipFree(s->d_tab_serial); hipFree(s->d_sh_jobs);
   if (s->xfer) { hipStreamSynchronize(s->xfer); hipStreamDestroy(s->xfer); }
   hipFree(s->d_ly_r[0]); hipFree(s->d_ly_r[1]); hipFree(s->d_ly_r[2]); hipFree(s->d_prev); hipFree(s->d_ovf_list); hipFree(s->d_ovf_list2);
@@ -1654,3 +1658,4 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
 
 #include "fsim_camera.hpp"
 #include "fsim_points.hpp"
+#include "fsim_voxels.hpp"

@@ -23,6 +23,26 @@ struct PtsGatherArgs {
   float lo[3], hi[3]; // crop box (+-inf: none)
 };
 
+// The world point of pixel p = cam*H*W + row*W + col at depth d (the header's formula): k_cam_ray's ray of pixel (col, row), turned and
+// moved by the camera pose k_cam_pose leaves (cpose: CAM_PW words per camera, cslope: the cameras' slopes).  k_pts_gather and k_vox_bin
+// (fsim_voxels.hpp) both call it, so a voxel's points are the dense map's bit for bit.  It is written out operation by operation, the
+// fused multiply-adds exactly where hipcc's default contraction put them when k_pts_gather held this code inline (every other product
+// and sum rounded on its own): left to the contraction, the same source compiled into two kernels can fuse different products (the
+// SLP vectorizer pairs the rows differently), and the two kernels' points then differ in the last bit.
+DEV V3 pts_point(const float *cpose, const float *cslope, int W, int H, int p, float d) {
+#pragma clang fp contract(off)
+  const int hw_ = W * H;
+  const float hw = 0.5f * W, hh = 0.5f * H;
+  const int cam = p / hw_, rem = p - cam * hw_, row = rem / W, col = rem - row * W;
+  const float s = cslope[cam];
+  const float cx = (col + 0.5f - hw) * s, cy = (hh - row - 0.5f) * s; // k_cam_ray's ray of pixel (col, row)
+  const float *c = cpose + CAM_PW * cam, *R = c + 3;                  // position, rotation (row-major)
+  const float m0 = __builtin_fmaf(R[1], cy, R[0] * cx) - R[2];        // R (cx, cy, -1)
+  const float m1 = __builtin_fmaf(R[3], cx, R[4] * cy) - R[5];
+  const float m2 = __builtin_fmaf(R[6], cx, R[7] * cy) - R[8];
+  return v3(__builtin_fmaf(m0, d, c[0]), __builtin_fmaf(m1, d, c[1]), __builtin_fmaf(m2, d, c[2])); // pos + (R ray) * depth
+}
+
 __global__ __launch_bounds__(PTS_GTHREADS) void k_pts_gather(PtsGatherArgs a, const float *__restrict__ pose, const float *__restrict__ depth,
                                                              const int *__restrict__ seg, const unsigned char *__restrict__ keep,
                                                              float *__restrict__ xyz, int *__restrict__ pseg, f4_t *__restrict__ cand,
@@ -35,21 +55,14 @@ __global__ __launch_bounds__(PTS_GTHREADS) void k_pts_gather(PtsGatherArgs a, co
   if (tid < FSIM_CAM_MAX) cslope[tid] = a.slope[tid];
   __syncthreads();
   const size_t base = (size_t)e * a.npix;
-  const int hw_ = a.W * a.H;
-  const float hw = 0.5f * a.W, hh = 0.5f * a.H;
   int total = 0, buf = 0;
   for (int p0 = 0; p0 < a.npix; p0 += PTS_GTHREADS) {
     const int p = p0 + tid;
     bool kept = false;
     V3 q = v3(0.0f, 0.0f, 0.0f);
     if (p < a.npix) {
-      const int cam = p / hw_, rem = p - cam * hw_, row = rem / a.W, col = rem - row * a.W;
-      const float s = cslope[cam];
-      const float cx = (col + 0.5f - hw) * s, cy = (hh - row - 0.5f) * s; // k_cam_ray's ray of pixel (col, row)
-      const V3 co = ldv3(cpose + CAM_PW * cam);
-      const M3 Rc = ldm3(cpose + CAM_PW * cam + 3);
       const int g = seg[base + p];
-      q = co + mulv(Rc, v3(cx, cy, -1.0f)) * depth[base + p];
+      q = pts_point(cpose, cslope, a.W, a.H, p, depth[base + p]);
       kept = g >= 0 && keep[g] && q.x >= a.lo[0] && q.y >= a.lo[1] && q.z >= a.lo[2] && q.x <= a.hi[0] && q.y <= a.hi[1] && q.z <= a.hi[2];
       if (a.dense) {
         stv3(xyz + 3 * (base + p), q);

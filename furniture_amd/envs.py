@@ -357,9 +357,10 @@ class FurnitureBatchEnv:
 
     cameras = None
     point_cloud = None
+    voxels = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -367,10 +368,17 @@ class FurnitureBatchEnv:
         (int32, model geom ids), [n, C, H, W] device tensors rendered from the collision geometry after the step's sync.
         point_cloud: a furniture_amd.points.PointCloud (needs cameras) -- the observations then also hold point_cloud (float32 world
         xyz, [n, N, 3]; dense mode [n, C, H, W, 3]), point_cloud_segmentation (int32 model geom id, -1 = padding) and point_cloud_count
-        (int32 [n], the kept pixels), built from the same render as the images."""
+        (int32 [n], the kept pixels), built from the same render as the images.
+        voxels: a furniture_amd.voxels.VoxelGrid (needs cameras) -- the observations then also hold voxel_count (int16 [n, dx, dy, dz],
+        kept pixels per cell, saturating at 32767) and voxel_segmentation (int16 [n, dx, dy, dz], model geom id of the cell's first kept
+        pixel, -1 = empty), binned from the same render as the images.  With point_cloud as well, each observation renders the cameras
+        twice (fsim_render_points, then fsim_render_voxels: two ray passes of the same state; the images are the second's)."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
+        if voxels is not None:
+            from .voxels import check as check_voxels
+            check_voxels(voxels, list(cameras) if cameras else None)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -480,6 +488,12 @@ class FurnitureBatchEnv:
             self._pts_out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
             for k, (sh, dt) in self.sim.points_shapes().items():
                 self._pts_out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
+        self.voxels = voxels
+        if voxels is not None:  # (without it: no allocation, no launch, the same observation dict)
+            self.sim.set_voxels(voxels)
+            self._vox_out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
+            for k, (sh, dt) in self.sim.voxels_shapes().items():
+                self._vox_out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -508,6 +522,9 @@ class FurnitureBatchEnv:
             sp.append(("point_cloud", spaces.Box(-np.inf, np.inf, shape=per + (3,), dtype=np.float32)))
             sp.append(("point_cloud_segmentation", spaces.Box(-1, self.model.ngeom - 1, shape=per, dtype=np.int32)))
             sp.append(("point_cloud_count", spaces.Box(0, int(np.prod(shape)), shape=(), dtype=np.int32)))
+        if self.voxels is not None:
+            sp.append(("voxel_count", spaces.Box(0, 32767, shape=self.voxels.dims, dtype=np.int16)))
+            sp.append(("voxel_segmentation", spaces.Box(-1, self.model.ngeom - 1, shape=self.voxels.dims, dtype=np.int16)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -518,13 +535,18 @@ class FurnitureBatchEnv:
 
     def _observe(self, subtask=None):
         """the observation dict of the state the last sync() left: _split of the slab, plus the camera images when cameras are set and
-        the point cloud when one is set (images and points from one fsim_render_points call: one ray pass)"""
+        the point cloud when one is set (images and points from one fsim_render_points call: one ray pass) and the voxel grid when one is
+        set (from one fsim_render_voxels call; with a point cloud as well, that is a second ray pass of the same state)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
             for k in ("camera_depth", "camera_segmentation", "point_cloud", "point_cloud_segmentation", "point_cloud_count"):
                 out[k] = res[k]
-        elif self.cameras:
+        if self.voxels is not None:
+            res = self.sim.render_voxels(images=True, out=self._vox_out)
+            for k in ("camera_depth", "camera_segmentation", "voxel_count", "voxel_segmentation"):
+                out[k] = res[k]
+        if self.cameras and self.point_cloud is None and self.voxels is None:
             out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
         return out
 
@@ -860,7 +882,7 @@ class _SingleEnv:
             dev = old.sim.device.index or 0
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
-                                         point_cloud=old.point_cloud)
+                                         point_cloud=old.point_cloud, voxels=old.voxels)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

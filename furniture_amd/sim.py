@@ -62,7 +62,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -163,6 +163,8 @@ def lib():
         L.fsim_render.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fsim_set_points.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         L.fsim_render_points.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6
+        L.fsim_set_voxels.argtypes = [ctypes.c_void_p] * 4
+        L.fsim_render_voxels.argtypes = [ctypes.c_void_p] * 5
         _LIB = L
     return _LIB
 
@@ -180,6 +182,8 @@ EXPORTED_SYMBOLS = [
 CAMERA_SYMBOLS = ["fsim_set_cameras", "fsim_render"]
 # the point-cloud entry points: a header of their own (include/fsim_points.h), exported by the same library
 POINTS_SYMBOLS = ["fsim_set_points", "fsim_render_points"]
+# the voxel-grid entry points: a header of their own (include/fsim_voxels.h), exported by the same library
+VOXELS_SYMBOLS = ["fsim_set_voxels", "fsim_render_voxels"]
 
 
 def preassembled_rows(model, preassembled):
@@ -525,6 +529,56 @@ class FSim:
         self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
         self._chk(lib().fsim_render_points(self._h, ptr("camera_depth"), ptr("camera_segmentation"), ptr("point_cloud"),
                                            ptr("point_cloud_segmentation"), ptr("point_cloud_pixel"), ptr("point_cloud_count")))
+        cur.wait_stream(self.torch_stream)
+        return res
+
+    # -- voxel grids from the cameras (include/fsim_voxels.h, furniture_amd/voxels.py) ----------------------------------------------
+    voxels = None
+
+    def set_voxels(self, spec):
+        """Set the voxel-grid settings (a furniture_amd.voxels.VoxelGrid); checked on the host first, then by the library."""
+        from .points import geom_keep
+        from .voxels import VoxelGrid
+        if not isinstance(spec, VoxelGrid):
+            raise TypeError("set_voxels: a furniture_amd.voxels.VoxelGrid, not %r" % type(spec).__name__)
+        keep = np.ascontiguousarray(geom_keep(self.cm, spec.include), dtype=np.uint8)
+        dims = np.ascontiguousarray(spec.dims, dtype=np.int32)
+        box = np.ascontiguousarray(spec.box, dtype=np.float32).reshape(6)
+        self._chk(lib().fsim_set_voxels(self._h, dims.ctypes.data, box.ctypes.data, keep.ctypes.data))
+        self.voxels = spec
+
+    def voxels_shapes(self):
+        """{key: (shape, dtype)} of render_voxels' outputs (without the n_envs dimension)"""
+        torch = self.torch
+        return {"voxel_count": (self.voxels.dims, torch.int16), "voxel_segmentation": (self.voxels.dims, torch.int16)}
+
+    def render_voxels(self, images=False, out=None):
+        """Render the cameras once and bin the images into the voxel grid (include/fsim_voxels.h), for the state sync() leaves -> dict of
+        device tensors [n, dx, dy, dz] (z fastest): voxel_count (int16 kept pixels per cell, saturating at 32767) and voxel_segmentation
+        (int16 model geom id of the cell's first kept pixel in (camera, row, column) order, -1 = empty), and with images=True
+        camera_depth / camera_segmentation [n, C, H, W] as FSim.render gives them.  out: a dict of such tensors to write into instead of
+        new ones.  Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if self.voxels is None:
+            raise FsimError("render_voxels: no voxel settings (FSim.set_voxels)")
+        if not self.cameras:
+            raise FsimError("render_voxels: no cameras set (FSim.set_cameras)")
+        want = self.voxels_shapes()
+        if images:
+            img = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+            want["camera_depth"], want["camera_segmentation"] = (img, torch.float32), (img, torch.int32)
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "render_voxels: out[%r] of the wrong shape / type" % k
+            res[k] = t
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_render_voxels(self._h, ptr("camera_depth"), ptr("camera_segmentation"), ptr("voxel_count"),
+                                           ptr("voxel_segmentation")))
         cur.wait_stream(self.torch_stream)
         return res
 

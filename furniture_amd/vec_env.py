@@ -48,6 +48,9 @@ class FurnitureVecEnv:
         if kw.pop("point_cloud", None) is not None:
             raise NotImplementedError("point_cloud= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., cameras=[...], point_cloud=PointCloud(...)), whose points stay on the device")
+        if kw.pop("voxels", None) is not None:
+            raise NotImplementedError("voxels= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., cameras=[...], voxels=VoxelGrid(...)), whose grids stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
