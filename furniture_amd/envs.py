@@ -358,9 +358,10 @@ class FurnitureBatchEnv:
     cameras = None
     point_cloud = None
     voxels = None
+    normals = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -372,13 +373,23 @@ class FurnitureBatchEnv:
         voxels: a furniture_amd.voxels.VoxelGrid (needs cameras) -- the observations then also hold voxel_count (int16 [n, dx, dy, dz],
         kept pixels per cell, saturating at 32767) and voxel_segmentation (int16 [n, dx, dy, dz], model geom id of the cell's first kept
         pixel, -1 = empty), binned from the same render as the images.  With point_cloud as well, each observation renders the cameras
-        twice (fsim_render_points, then fsim_render_voxels: two ray passes of the same state; the images are the second's)."""
+        twice (fsim_render_points, then fsim_render_voxels: two ray passes of the same state; the images are the second's).
+        normals: a furniture_amd.normals.Normals (needs cameras) -- the observations then also hold camera_normal (float32
+        [n, C, H, W, 3], the world-frame unit outward normal of the surface each pixel sees, (0, 0, 0) where it sees nothing) and / or
+        camera_shaded (uint8 [n, C, H, W, 4], a Lambert-shaded colour-by-part RGBA picture of the collision geometry), as the settings
+        ask.  With cameras and normals alone, images and normals come from one fsim_render_normals call.  With point_cloud as well, the
+        observations also hold point_cloud_normal (float32, the shape of point_cloud: camera_normal gathered at the sampled pixels,
+        (0, 0, 0) for padding; dense mode: camera_normal with (0, 0, 0) where point_cloud_segmentation is -1), and the cameras are
+        rendered once more (fsim_render_points, then fsim_render_normals: one more ray pass of the same state, as with voxels)."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
         if voxels is not None:
             from .voxels import check as check_voxels
             check_voxels(voxels, list(cameras) if cameras else None)
+        if normals is not None:
+            from .normals import check as check_normals
+            check_normals(normals, list(cameras) if cameras else None)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -494,6 +505,12 @@ class FurnitureBatchEnv:
             self._vox_out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
             for k, (sh, dt) in self.sim.voxels_shapes().items():
                 self._vox_out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
+        self.normals = normals
+        if normals is not None:  # (without it: no allocation, no launch, the same observation dict)
+            self.sim.set_normals(normals)
+            self._nrm_out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
+            for k, (sh, dt) in self.sim.normals_shapes().items():
+                self._nrm_out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -525,6 +542,13 @@ class FurnitureBatchEnv:
         if self.voxels is not None:
             sp.append(("voxel_count", spaces.Box(0, 32767, shape=self.voxels.dims, dtype=np.int16)))
             sp.append(("voxel_segmentation", spaces.Box(-1, self.model.ngeom - 1, shape=self.voxels.dims, dtype=np.int16)))
+        if self.normals is not None:
+            if self.normals.normal:
+                sp.append(("camera_normal", spaces.Box(-1.0, 1.0, shape=shape + (3,), dtype=np.float32)))
+            if self.normals.shaded:
+                sp.append(("camera_shaded", spaces.Box(0, 255, shape=shape + (4,), dtype=np.uint8)))
+            if self.normals.normal and self.point_cloud is not None:
+                sp.append(("point_cloud_normal", spaces.Box(-1.0, 1.0, shape=per + (3,), dtype=np.float32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -536,7 +560,8 @@ class FurnitureBatchEnv:
     def _observe(self, subtask=None):
         """the observation dict of the state the last sync() left: _split of the slab, plus the camera images when cameras are set and
         the point cloud when one is set (images and points from one fsim_render_points call: one ray pass) and the voxel grid when one is
-        set (from one fsim_render_voxels call; with a point cloud as well, that is a second ray pass of the same state)"""
+        set (from one fsim_render_voxels call; with a point cloud as well, that is a second ray pass of the same state) and the normal /
+        shaded images when they are set (from one fsim_render_normals call, after the others: one more ray pass when there are any)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -546,9 +571,26 @@ class FurnitureBatchEnv:
             res = self.sim.render_voxels(images=True, out=self._vox_out)
             for k in ("camera_depth", "camera_segmentation", "voxel_count", "voxel_segmentation"):
                 out[k] = res[k]
-        if self.cameras and self.point_cloud is None and self.voxels is None:
+        if self.normals is not None:
+            res = self.sim.render_normals(images=True, out=self._nrm_out)
+            for k in ("camera_depth", "camera_segmentation", "camera_normal", "camera_shaded"):
+                if k in res:
+                    out[k] = res[k]
+            if self.normals.normal and self.point_cloud is not None:
+                out["point_cloud_normal"] = self._point_normals(res["camera_normal"])
+        if self.cameras and self.point_cloud is None and self.voxels is None and self.normals is None:
             out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
         return out
+
+    def _point_normals(self, normal):
+        """camera_normal at the point cloud's pixels: dense mode masks the image where the dense label is -1; sampled mode gathers at
+        point_cloud_pixel ((0, 0, 0) for the padding of an env without kept pixels)"""
+        torch = self.sim.torch
+        if self.point_cloud.dense:
+            return torch.where((self._pts_out["point_cloud_segmentation"] >= 0).unsqueeze(-1), normal, torch.zeros_like(normal))
+        pix = self._pts_out["point_cloud_pixel"]
+        got = torch.gather(normal.reshape(normal.shape[0], -1, 3), 1, pix.clamp(min=0).long().unsqueeze(-1).expand(-1, -1, 3))
+        return torch.where((pix >= 0).unsqueeze(-1), got, torch.zeros_like(got))
 
     @property
     def action_space(self):
@@ -882,7 +924,7 @@ class _SingleEnv:
             dev = old.sim.device.index or 0
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
-                                         point_cloud=old.point_cloud, voxels=old.voxels)
+                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())
@@ -902,7 +944,12 @@ class _SingleEnv:
 
     def render(self, mode="human"):
         """"depth_array": the depth image [H, W] (metres) of camera 0 of the current state (needs cameras=[...]).  RGB ("rgb_array",
-        "human") is not available: the compiled models hold no visual meshes, only the collision geometry the cameras see."""
+        "human") is not available: the compiled models hold no visual meshes, only the collision geometry the cameras see.
+        "normal_array": the world-frame surface normals [H, W, 3] float32 of camera 0; "shaded_array": a Lambert-shaded colour-by-part
+        picture [H, W, 3] uint8 of the collision geometry from camera 0 (the env's normals= settings when it has them, else the defaults
+        of furniture_amd.normals.Normals)."""
+        if mode in ("normal_array", "shaded_array"):
+            return self._render_normals(mode)
         if mode != "depth_array":
             raise NotImplementedError("render(%r): RGB rendering needs the reference's visual meshes (not part of the compiled model) and "
                                       "the Unity / MuJoCo viewer, both outside the accelerated hot path; render('depth_array') gives the "
@@ -912,6 +959,27 @@ class _SingleEnv:
         self._b.sim.sync()
         depth, _ = self._b.sim.render(segmentation=False)
         return depth[0, 0].cpu().numpy()
+
+    def _render_normals(self, mode):
+        from .normals import Normals
+        if not self._b.cameras:
+            raise ValueError("render(%r) needs cameras: make the env with cameras=[furniture_amd.camera.Camera(...)]" % mode)
+        sim, key = self._b.sim, "camera_normal" if mode == "normal_array" else "camera_shaded"
+        sim.sync()
+        keep = sim.normals
+        if keep is None or not (keep.normal if mode == "normal_array" else keep.shaded):
+            base = keep if keep is not None else Normals()
+            sim.set_normals(Normals(normal=mode == "normal_array", shaded=mode == "shaded_array", palette=base.palette, background=base.background,
+                                    ambient=base.ambient))
+        try:
+            img = sim.render_normals()[key][0, 0].cpu().numpy()
+        finally:
+            if keep is not sim.normals:  # the env's own settings (its observation buffers are sized for them)
+                if keep is not None:
+                    sim.set_normals(keep)
+                else:  # (the handle keeps the temporary settings, unused: FSim.render_normals refuses without FSim.normals, and an env
+                    sim.normals = None  # without normals= never calls it; the next render("..._array") sets them again)
+        return img if mode == "normal_array" else np.ascontiguousarray(img[:, :, :3])
 
     def close(self):
         self._b.close()

@@ -62,7 +62,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -165,6 +165,8 @@ def lib():
         L.fsim_render_points.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 6
         L.fsim_set_voxels.argtypes = [ctypes.c_void_p] * 4
         L.fsim_render_voxels.argtypes = [ctypes.c_void_p] * 5
+        L.fsim_set_normals.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float]
+        L.fsim_render_normals.argtypes = [ctypes.c_void_p] * 5
         _LIB = L
     return _LIB
 
@@ -184,6 +186,8 @@ CAMERA_SYMBOLS = ["fsim_set_cameras", "fsim_render"]
 POINTS_SYMBOLS = ["fsim_set_points", "fsim_render_points"]
 # the voxel-grid entry points: a header of their own (include/fsim_voxels.h), exported by the same library
 VOXELS_SYMBOLS = ["fsim_set_voxels", "fsim_render_voxels"]
+# the normal / shaded image entry points: a header of their own (include/fsim_normals.h), exported by the same library
+NORMALS_SYMBOLS = ["fsim_set_normals", "fsim_render_normals"]
 
 
 def preassembled_rows(model, preassembled):
@@ -579,6 +583,59 @@ class FSim:
         self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
         self._chk(lib().fsim_render_voxels(self._h, ptr("camera_depth"), ptr("camera_segmentation"), ptr("voxel_count"),
                                            ptr("voxel_segmentation")))
+        cur.wait_stream(self.torch_stream)
+        return res
+
+    # -- normal / shaded images from the cameras (include/fsim_normals.h, furniture_amd/normals.py) ----------------------------------
+    normals = None
+
+    def set_normals(self, spec):
+        """Set the normal / shaded image settings (a furniture_amd.normals.Normals); checked on the host first, then by the library."""
+        from .normals import Normals
+        if not isinstance(spec, Normals):
+            raise TypeError("set_normals: a furniture_amd.normals.Normals, not %r" % type(spec).__name__)
+        pal = spec.palette_for(self.cm)
+        bg = np.ascontiguousarray(spec.background, dtype=np.uint8)
+        self._chk(lib().fsim_set_normals(self._h, pal.ctypes.data if pal is not None else None, bg.ctypes.data, spec.ambient))
+        self.normals = spec
+
+    def normals_shapes(self):
+        """{key: (shape, dtype)} of render_normals' outputs (without the n_envs dimension)"""
+        torch = self.torch
+        img = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+        out = {}
+        if self.normals.normal:
+            out["camera_normal"] = (img + (3,), torch.float32)
+        if self.normals.shaded:
+            out["camera_shaded"] = (img + (4,), torch.uint8)
+        return out
+
+    def render_normals(self, images=False, out=None):
+        """Render the cameras once and derive the normal and / or shaded image (include/fsim_normals.h), for the state sync() leaves ->
+        dict of device tensors: camera_normal (float32 [n, C, H, W, 3], the world-frame unit outward normal of the surface the pixel
+        sees, (0, 0, 0) where it sees nothing) and / or camera_shaded (uint8 [n, C, H, W, 4], RGBA), as the settings ask, and with
+        images=True camera_depth / camera_segmentation [n, C, H, W] as FSim.render gives them.  out: a dict of such tensors to write
+        into instead of new ones.  Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if self.normals is None:
+            raise FsimError("render_normals: no normals settings (FSim.set_normals)")
+        if not self.cameras:
+            raise FsimError("render_normals: no cameras set (FSim.set_cameras)")
+        want = self.normals_shapes()
+        if images:
+            img = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+            want["camera_depth"], want["camera_segmentation"] = (img, torch.float32), (img, torch.int32)
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "render_normals: out[%r] of the wrong shape / type" % k
+            res[k] = t
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_render_normals(self._h, ptr("camera_depth"), ptr("camera_segmentation"), ptr("camera_normal"), ptr("camera_shaded")))
         cur.wait_stream(self.torch_stream)
         return res
 

@@ -51,6 +51,9 @@ class FurnitureVecEnv:
         if kw.pop("voxels", None) is not None:
             raise NotImplementedError("voxels= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., cameras=[...], voxels=VoxelGrid(...)), whose grids stay on the device")
+        if kw.pop("normals", None) is not None:
+            raise NotImplementedError("normals= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., cameras=[...], normals=Normals(...)), whose images stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
