@@ -9,6 +9,8 @@
 //               it against the frustum of its 16 x 16 quarter into a wave-uniform list (bounding spheres; planes always kept) and each
 //               lane casts the rays of four pixels of one column against that list in closed form, in the geom's frame.
 // No atomics: every pixel is written once, by one lane, and an env's image depends on nothing but its record and the camera set.
+// What fsim_points.hpp, fsim_voxels.hpp and fsim_normals.hpp share is here too, as plain functions: CamView and cam_stage_views for
+// their kernels, cam_view and cam_render_images (with the handle's one image scratch) for their host parts.
 #include "../../include/fsim_camera.h"
 
 #define CAM_PW 12 // scratch words per pose: position 3, rotation 9 (row-major, local -> world)
@@ -97,6 +99,19 @@ struct CamRayArgs {
   float slope[FSIM_CAM_MAX]; // tan(fovy / 2) / (H / 2): camera-frame x / y per pixel at unit depth
   float znear[FSIM_CAM_MAX], zfar[FSIM_CAM_MAX];
 };
+
+// What a kernel that reads the rendered images needs of the camera set (cam_view fills it): k_pts_gather, k_vox_bin, k_cam_normal
+struct CamView {
+  int ncam, W, H, npix /* ncam * W * H */, ncg, pstride;
+  float slope[FSIM_CAM_MAX];
+};
+
+// Stage what pts_point reads in LDS: the camera rows of the env's pose scratch (P: already at them, pose + e * pstride + CAM_PW * ncg)
+// as cpose [FSIM_CAM_MAX][CAM_PW] and the slopes as cslope [FSIM_CAM_MAX].  The caller's barrier follows.
+DEV void cam_stage_views(float *cpose, float *cslope, const float *P, const CamView &v, int tid, int nt) {
+  for (int i = tid; i < CAM_PW * v.ncam; i += nt) cpose[i] = P[i];
+  if (tid < FSIM_CAM_MAX) cslope[tid] = v.slope[tid];
+}
 
 #define CAM_INF 3.0e38f
 // [t0, t1]: the ray o + t d (geom frame) inside the solid; false: it misses.  Planes are infinite half-spaces (as they collide) whose
@@ -189,7 +204,8 @@ __global__ __launch_bounds__(256) void k_cam_ray(CamRayArgs a, const float *__re
   const int cam = blk % a.ncam, e = blk / a.ncam;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const float *P = pose + (size_t)e * a.pstride;
-  // stage the env's geom table and the hull planes
+  // stage the env's geom table and the hull planes (k_cam_normal holds the same three loops: moved into a shared function, the compiler
+  // unrolled them differently here and the smallest render measured slower, so they stay written out -- DESIGN.md 11)
   for (int i = tid; i < CAM_PW * a.ncg; i += 256) G[CAM_GW * (i / CAM_PW) + i % CAM_PW] = P[i];
   for (int i = tid; i < CAM_SW * a.ncg; i += 256) G[CAM_GW * (i / CAM_SW) + CAM_PW + i % CAM_SW] = cgtab[i];
   for (int i = tid; i < 4 * a.nplanes; i += 256) PL[i] = planes_g[i];
@@ -266,11 +282,13 @@ struct CamState {
   int ncam = 0, W = 0, H = 0, nplanes = 0, pstride = 0;
   float slope[FSIM_CAM_MAX] = {}, znear[FSIM_CAM_MAX] = {}, zfar[FSIM_CAM_MAX] = {};
   float *d_cams = nullptr, *d_cg = nullptr, *d_planes = nullptr, *d_pose = nullptr;
+  float *d_depth = nullptr; int *d_seg = nullptr; // image scratch of the derived observations (cam_render_images), [n_envs * npix]
 };
 
 static void cam_free(fsim *s) {
   if (!s->cam) return;
   hipFree(s->cam->d_cams); hipFree(s->cam->d_cg); hipFree(s->cam->d_planes); hipFree(s->cam->d_pose);
+  hipFree(s->cam->d_depth); hipFree(s->cam->d_seg);
   delete s->cam;
   s->cam = nullptr;
 }
@@ -381,4 +399,27 @@ extern "C" int fsim_render(fsim_t *s, float *depth_dev, int32_t *seg_dev) {
   hipLaunchKernelGGL(k_cam_ray, dim3((unsigned)nblk), dim3(256), lds, s->stream, ra, k.d_pose, k.d_cg, k.d_planes, depth_dev, seg_dev);
   HIPCHK(hipGetLastError());
   return FSIM_OK;
+}
+
+static CamView cam_view(const fsim *s) {
+  const CamState &k = *s->cam;
+  CamView v{};
+  v.ncam = k.ncam; v.W = k.W; v.H = k.H; v.npix = k.ncam * k.W * k.H; v.ncg = s->m.ncg; v.pstride = k.pstride;
+  for (int i = 0; i < FSIM_CAM_MAX; i++) v.slope[i] = k.slope[i];
+  return v;
+}
+
+// The render of fsim_render_points / _voxels / _normals (cameras set, device current): fsim_render into the caller's images, and for a
+// NULL one into the handle's image scratch -- one for the three of them, allocated on first use.  It lives as long as the camera set:
+// the image size changes with fsim_set_cameras alone, which waits for the stream and then frees it (cam_free).  *depth, *seg: the
+// images to read.
+static int cam_render_images(fsim *s, float *depth_dev, int32_t *seg_dev, const float **depth, const int **seg) {
+  CamState &k = *s->cam;
+  const size_t nimg = (size_t)s->n_envs * k.ncam * k.W * k.H;
+  if (!depth_dev && !k.d_depth) HIPCHK(hipMalloc(&k.d_depth, nimg * 4));
+  if (!seg_dev && !k.d_seg) HIPCHK(hipMalloc(&k.d_seg, nimg * 4));
+  float *d = depth_dev ? depth_dev : k.d_depth;
+  int *g = seg_dev ? seg_dev : k.d_seg;
+  *depth = d; *seg = g;
+  return fsim_render(s, d, g); // settles, then k_cam_pose + k_cam_ray
 }

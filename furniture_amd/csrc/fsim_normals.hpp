@@ -1,6 +1,7 @@
 // fsim_normals.hpp -- surface-normal and shaded images from the cameras (include/fsim_normals.h).  Included at the end of fsim.hip,
-// after fsim_voxels.hpp: the host part runs fsim_render (k_cam_pose, k_cam_ray, as they are) and reads the geom and camera poses
-// k_cam_pose leaves in the handle's pose scratch; the kernel back-projects through pts_point, the function k_pts_gather and k_vox_bin call.
+// after fsim_voxels.hpp: the host part renders through cam_render_images (fsim_render: k_cam_pose, k_cam_ray, as they are); the kernel
+// stages the geom poses k_cam_pose leaves in the handle's pose scratch as k_cam_ray does and the camera poses with
+// cam_stage_views, and back-projects through pts_point, the function k_pts_gather and k_vox_bin call.
 //
 // After fsim_render's two launches, on the same stream:
 //   k_cam_normal  one 256-thread workgroup per (env, camera, chunk of up to NRM_CHUNK pixels).  The env's geom table (pose + static
@@ -19,8 +20,8 @@
 #define NRM_NOGEOM 0xff // id table: a model geom that does not collide (never seen by a camera)
 
 struct NrmArgs {
-  int ncam, W, H, hw /* W * H */, npix /* ncam * hw */, ncg, ngeom, nplanes, pstride, nchunk;
-  float slope[FSIM_CAM_MAX];
+  CamView v;
+  int hw /* W * H */, ngeom, nplanes, nchunk;
   float ambient;
   unsigned background; // RGBA, R in the low byte
 };
@@ -72,24 +73,23 @@ __global__ __launch_bounds__(NRM_THREADS) void k_cam_normal(NrmArgs a, const flo
                                                             const int *__restrict__ seg, float *__restrict__ normal, unsigned *__restrict__ shaded) {
   extern __shared__ float nrm_lds[];
   float *G = nrm_lds;                      // [ncg][CAM_GW]
-  float *PL = G + CAM_GW * a.ncg;          // [nplanes][4]
+  float *PL = G + CAM_GW * a.v.ncg;        // [nplanes][4]
   float *cpose = PL + 4 * a.nplanes;       // [FSIM_CAM_MAX][CAM_PW]
   float *cslope = cpose + FSIM_CAM_MAX * CAM_PW; // [FSIM_CAM_MAX]
   unsigned char *idtab = reinterpret_cast<unsigned char *>(cslope + FSIM_CAM_MAX); // [ngeom]
   int blk = blockIdx.x;
   const int chunk = blk % a.nchunk; blk /= a.nchunk;
-  const int cam = blk % a.ncam, e = blk / a.ncam, tid = threadIdx.x;
-  const float *P = pose + (size_t)e * a.pstride;
-  for (int i = tid; i < CAM_PW * a.ncg; i += NRM_THREADS) G[CAM_GW * (i / CAM_PW) + i % CAM_PW] = P[i];
-  for (int i = tid; i < CAM_SW * a.ncg; i += NRM_THREADS) G[CAM_GW * (i / CAM_SW) + CAM_PW + i % CAM_SW] = cgtab[i];
+  const int cam = blk % a.v.ncam, e = blk / a.v.ncam, tid = threadIdx.x;
+  const float *P = pose + (size_t)e * a.v.pstride;
+  for (int i = tid; i < CAM_PW * a.v.ncg; i += NRM_THREADS) G[CAM_GW * (i / CAM_PW) + i % CAM_PW] = P[i]; // (k_cam_ray's three loops)
+  for (int i = tid; i < CAM_SW * a.v.ncg; i += NRM_THREADS) G[CAM_GW * (i / CAM_SW) + CAM_PW + i % CAM_SW] = cgtab[i];
   for (int i = tid; i < 4 * a.nplanes; i += NRM_THREADS) PL[i] = planes_g[i];
-  for (int i = tid; i < CAM_PW * a.ncam; i += NRM_THREADS) cpose[i] = P[CAM_PW * a.ncg + i];
-  if (tid < FSIM_CAM_MAX) cslope[tid] = a.slope[tid];
+  cam_stage_views(cpose, cslope, P + CAM_PW * a.v.ncg, a.v, tid, NRM_THREADS);
   for (int i = tid; i < a.ngeom; i += NRM_THREADS) idtab[i] = idtab_g[i];
   __syncthreads();
   const V3 co = ldv3(cpose + CAM_PW * cam);
   const int c0 = chunk * NRM_CHUNK, len = min(NRM_CHUNK, a.hw - c0); // this workgroup's pixels of the (env, camera) image
-  const size_t img = (size_t)e * a.npix + (size_t)cam * a.hw + c0;    // the first of them, in pixels of the whole batch
+  const size_t img = (size_t)e * a.v.npix + (size_t)cam * a.hw + c0;    // the first of them, in pixels of the whole batch
   for (int r0 = 0; r0 < len; r0 += NRM_THREADS) {
     const int r = r0 + tid;
     V3 n = v3(0.0f, 0.0f, 0.0f);
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(NRM_THREADS) void k_cam_normal(NrmArgs a, const flo
       const int g = seg[img + r];
       unsigned px = a.background;
       if (g >= 0 && g < a.ngeom) {
-        const V3 q = pts_point(cpose, cslope, a.W, a.H, cam * a.hw + c0 + r, depth[img + r]);
+        const V3 q = pts_point(cpose, cslope, a.v.W, a.v.H, cam * a.hw + c0 + r, depth[img + r]);
         const int ci = idtab[g];
         if (ci != NRM_NOGEOM) { // (always: the ray pass names colliding geoms only; otherwise the normal stays (0, 0, 0))
           const float *Gg = G + CAM_GW * ci;
@@ -127,13 +127,11 @@ struct NrmState {
   unsigned background = 0u;
   unsigned *d_palette = nullptr;                  // [ngeom] RGBA, R in the low byte
   unsigned char *d_idtab = nullptr;               // [ngeom] model geom id -> colliding geom (row of the staged table), NRM_NOGEOM: none
-  float *d_depth = nullptr; int *d_seg = nullptr; // image scratch (a NULL depth / seg of fsim_render_normals), [n_envs * npix]
-  size_t cap_img = 0;                             // elements allocated
 };
 
 static void nrm_free(fsim *s) {
   if (!s->nrm) return;
-  hipFree(s->nrm->d_palette); hipFree(s->nrm->d_idtab); hipFree(s->nrm->d_depth); hipFree(s->nrm->d_seg);
+  hipFree(s->nrm->d_palette); hipFree(s->nrm->d_idtab);
   delete s->nrm;
   s->nrm = nullptr;
 }
@@ -178,29 +176,17 @@ extern "C" int fsim_render_normals(fsim_t *s, float *depth_dev, int32_t *seg_dev
   if (shaded_dev && !v.has_palette) FAIL(FSIM_EINVAL, "fsim_render_normals: shaded_dev given without a palette (fsim_set_normals)");
   if (reinterpret_cast<uintptr_t>(shaded_dev) & 3) FAIL(FSIM_EINVAL, "fsim_render_normals: shaded_dev is not 4-byte aligned");
   const int hw = k.W * k.H;
-  const long npix = (long)k.ncam * hw;
   const int nchunk = (hw + NRM_CHUNK - 1) / NRM_CHUNK;
   const size_t nblk = (size_t)s->n_envs * k.ncam * nchunk;
   if (nblk > 0x7fffffff) FAIL(FSIM_EINVAL, "fsim_render_normals: %zu workgroups", nblk);
   const size_t lds = 4 * ((size_t)CAM_GW * s->m.ncg + 4 * k.nplanes + FSIM_CAM_MAX * CAM_PW + FSIM_CAM_MAX) + (size_t)s->ngeom;
   if (lds > 65536) FAIL(FSIM_EINVAL, "fsim_render_normals: %d geoms need %zu bytes of LDS (at most 65536)", s->ngeom, lds);
   HIPCHK(hipSetDevice(s->device));
-  const size_t nimg = (size_t)s->n_envs * npix;
-  if ((!depth_dev || !seg_dev) && v.cap_img < nimg) { // scratch, allocated on first use and grown with the image size
-    HIPCHK(hipStreamSynchronize(s->stream));
-    hipFree(v.d_depth); hipFree(v.d_seg);
-    v.d_depth = nullptr; v.d_seg = nullptr; v.cap_img = 0;
-    HIPCHK(hipMalloc(&v.d_depth, nimg * 4));
-    HIPCHK(hipMalloc(&v.d_seg, nimg * 4));
-    v.cap_img = nimg;
-  }
-  float *depth = depth_dev ? depth_dev : v.d_depth;
-  int *seg = seg_dev ? seg_dev : v.d_seg;
-  { int rc_ = fsim_render(s, depth, seg); if (rc_) return rc_; } // settles, then k_cam_pose + k_cam_ray
+  const float *depth;
+  const int *seg;
+  { int rc_ = cam_render_images(s, depth_dev, seg_dev, &depth, &seg); if (rc_) return rc_; }
   NrmArgs na{};
-  na.ncam = k.ncam; na.W = k.W; na.H = k.H; na.hw = hw; na.npix = (int)npix; na.ncg = s->m.ncg; na.ngeom = s->ngeom; na.nplanes = k.nplanes;
-  na.pstride = k.pstride; na.nchunk = nchunk; na.ambient = v.ambient; na.background = v.background;
-  for (int i = 0; i < FSIM_CAM_MAX; i++) na.slope[i] = k.slope[i];
+  na.v = cam_view(s); na.hw = hw; na.ngeom = s->ngeom; na.nplanes = k.nplanes; na.nchunk = nchunk; na.ambient = v.ambient; na.background = v.background;
   hipLaunchKernelGGL(k_cam_normal, dim3((unsigned)nblk), dim3(NRM_THREADS), lds, s->stream, na, k.d_pose, k.d_cg, k.d_planes, v.d_idtab, v.d_palette,
                      depth, seg, normal_dev, reinterpret_cast<unsigned *>(shaded_dev));
   HIPCHK(hipGetLastError());

@@ -1,6 +1,7 @@
 // fsim_points.hpp -- point-cloud observations built from the cameras (include/fsim_points.h).  Included at the end of fsim.hip, after
-// fsim_camera.hpp: the host part runs fsim_render (k_cam_pose, k_cam_ray, as they are) and reads the camera poses k_cam_pose leaves in
-// the handle's pose scratch.
+// fsim_camera.hpp: the host part renders through cam_render_images (fsim_render: k_cam_pose, k_cam_ray, as they are) and the kernel
+// stages the camera poses k_cam_pose leaves in the handle's pose scratch with cam_stage_views.  The kept-pixel rule (pts_seg_kept,
+// pts_in_box) and the keep-table / box helpers of the settings calls are here for fsim_voxels.hpp as well.
 //
 // After fsim_render's two launches, on the same stream:
 //   k_pts_gather  one 256-thread workgroup per env: back-projects every pixel of the env's images to the world frame, applies the
@@ -18,8 +19,8 @@
 #define PTS_FTHREADS 512 // k_pts_fps
 
 struct PtsGatherArgs {
-  int ncam, W, H, npix /* ncam * W * H */, ncg, pstride, dense;
-  float slope[FSIM_CAM_MAX];
+  CamView v;
+  int dense;
   float lo[3], hi[3]; // crop box (+-inf: none)
 };
 
@@ -43,6 +44,13 @@ DEV V3 pts_point(const float *cpose, const float *cslope, int W, int H, int p, f
   return v3(__builtin_fmaf(m0, d, c[0]), __builtin_fmaf(m1, d, c[1]), __builtin_fmaf(m2, d, c[2])); // pos + (R ray) * depth
 }
 
+// The kept-pixel rule of the header, in its two halves: the pixel sees a geom of the keep table (k_vox_bin asks this one first and
+// back-projects only then), and its world point lies in the closed box.
+DEV bool pts_seg_kept(int g, const unsigned char *keep) { return g >= 0 && keep[g]; }
+DEV bool pts_in_box(V3 q, const float *lo, const float *hi) {
+  return q.x >= lo[0] && q.y >= lo[1] && q.z >= lo[2] && q.x <= hi[0] && q.y <= hi[1] && q.z <= hi[2];
+}
+
 __global__ __launch_bounds__(PTS_GTHREADS) void k_pts_gather(PtsGatherArgs a, const float *__restrict__ pose, const float *__restrict__ depth,
                                                              const int *__restrict__ seg, const unsigned char *__restrict__ keep,
                                                              float *__restrict__ xyz, int *__restrict__ pseg, f4_t *__restrict__ cand,
@@ -50,20 +58,18 @@ __global__ __launch_bounds__(PTS_GTHREADS) void k_pts_gather(PtsGatherArgs a, co
   __shared__ float cpose[FSIM_CAM_MAX * CAM_PW], cslope[FSIM_CAM_MAX];
   __shared__ int wcnt[2][PTS_GTHREADS / 64];
   const int e = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const float *P = pose + (size_t)e * a.pstride + CAM_PW * a.ncg; // the camera rows of the env's pose scratch
-  for (int i = tid; i < CAM_PW * a.ncam; i += PTS_GTHREADS) cpose[i] = P[i];
-  if (tid < FSIM_CAM_MAX) cslope[tid] = a.slope[tid];
+  cam_stage_views(cpose, cslope, pose + (size_t)e * a.v.pstride + CAM_PW * a.v.ncg, a.v, tid, PTS_GTHREADS);
   __syncthreads();
-  const size_t base = (size_t)e * a.npix;
+  const size_t base = (size_t)e * a.v.npix;
   int total = 0, buf = 0;
-  for (int p0 = 0; p0 < a.npix; p0 += PTS_GTHREADS) {
+  for (int p0 = 0; p0 < a.v.npix; p0 += PTS_GTHREADS) {
     const int p = p0 + tid;
     bool kept = false;
     V3 q = v3(0.0f, 0.0f, 0.0f);
-    if (p < a.npix) {
+    if (p < a.v.npix) {
       const int g = seg[base + p];
-      q = pts_point(cpose, cslope, a.W, a.H, p, depth[base + p]);
-      kept = g >= 0 && keep[g] && q.x >= a.lo[0] && q.y >= a.lo[1] && q.z >= a.lo[2] && q.x <= a.hi[0] && q.y <= a.hi[1] && q.z <= a.hi[2];
+      q = pts_point(cpose, cslope, a.v.W, a.v.H, p, depth[base + p]);
+      kept = pts_seg_kept(g, keep) && pts_in_box(q, a.lo, a.hi);
       if (a.dense) {
         stv3(xyz + 3 * (base + p), q);
         pseg[base + p] = kept ? g : -1;
@@ -179,45 +185,54 @@ __global__ __launch_bounds__(PTS_FTHREADS) void k_pts_fps(int npix, int n_points
 struct PtsState {
   int n_points = 0;
   float lo[3], hi[3];
-  unsigned char *d_keep = nullptr;                       // [ngeom]
-  float *d_depth = nullptr; int *d_seg = nullptr;        // image scratch (a NULL depth / seg of fsim_render_points), [n_envs * npix]
-  f4_t *d_cand = nullptr;                                // candidates (sampled mode), [n_envs * npix]
-  size_t cap_img = 0, cap_cand = 0;                      // elements allocated
+  unsigned char *d_keep = nullptr; // [ngeom]
+  f4_t *d_cand = nullptr;          // candidates (sampled mode), [n_envs * npix]
+  size_t cap_cand = 0;             // elements allocated
 };
 
 static void pts_free(fsim *s) {
   if (!s->pts) return;
-  hipFree(s->pts->d_keep); hipFree(s->pts->d_depth); hipFree(s->pts->d_seg); hipFree(s->pts->d_cand);
+  hipFree(s->pts->d_keep); hipFree(s->pts->d_cand);
   delete s->pts;
   s->pts = nullptr;
+}
+
+// the finite half of the two box rules (who: the entry point, for the message)
+static int pts_box_finite(const char *who, const float *box) {
+  for (int i = 0; i < 6; i++)
+    if (!std::isfinite(box[i])) FAIL(FSIM_EINVAL, "%s: box bound %d is not finite", who, i);
+  return FSIM_OK;
+}
+
+// The geom_keep table of fsim_set_points / fsim_set_voxels on the device, [max(ngeom, 1)] bytes (NULL: every geom kept): *d_keep is
+// allocated by the first call.  The caller has waited for the stream: a render in flight still reads the old table.
+static int pts_upload_keep(fsim *s, const uint8_t *geom_keep, unsigned char **d_keep) {
+  std::vector<unsigned char> keep(std::max(s->ngeom, 1), 1);
+  if (geom_keep)
+    for (int g = 0; g < s->ngeom; g++) keep[g] = geom_keep[g] ? 1 : 0;
+  if (!*d_keep) HIPCHK(hipMalloc(d_keep, keep.size()));
+  HIPCHK(hipMemcpy(*d_keep, keep.data(), keep.size(), hipMemcpyHostToDevice));
+  return FSIM_OK;
 }
 
 extern "C" int fsim_set_points(fsim_t *s, int n_points, const uint8_t *geom_keep, const float *box) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_points: null handle");
   if (n_points < 0 || n_points > FSIM_PTS_MAX_POINTS) FAIL(FSIM_EINVAL, "fsim_set_points: n_points %d (0 .. %d)", n_points, FSIM_PTS_MAX_POINTS);
   if (box) {
-    for (int i = 0; i < 6; i++)
-      if (!std::isfinite(box[i])) FAIL(FSIM_EINVAL, "fsim_set_points: box bound %d is not finite", i);
+    if (pts_box_finite("fsim_set_points", box)) return FSIM_EINVAL;
     for (int i = 0; i < 3; i++)
       if (box[i] > box[3 + i]) FAIL(FSIM_EINVAL, "fsim_set_points: box lo %g > hi %g on axis %d", box[i], box[3 + i], i);
   }
-  std::vector<unsigned char> keep(std::max(s->ngeom, 1), 1);
-  if (geom_keep)
-    for (int g = 0; g < s->ngeom; g++) keep[g] = geom_keep[g] ? 1 : 0;
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipStreamSynchronize(s->stream)); // (a render in flight still reads the old keep table)
-  if (!s->pts) {
-    s->pts = new PtsState();
-    HIPCHK(hipMalloc(&s->pts->d_keep, keep.size()));
-  }
+  if (!s->pts) s->pts = new PtsState();
   PtsState &p = *s->pts;
   p.n_points = n_points;
   for (int i = 0; i < 3; i++) {
     p.lo[i] = box ? box[i] : -INFINITY;
     p.hi[i] = box ? box[3 + i] : INFINITY;
   }
-  HIPCHK(hipMemcpy(p.d_keep, keep.data(), keep.size(), hipMemcpyHostToDevice));
-  return FSIM_OK;
+  return pts_upload_keep(s, geom_keep, &p.d_keep);
 }
 
 extern "C" int fsim_render_points(fsim_t *s, float *depth_dev, int32_t *seg_dev, float *xyz_dev, int32_t *pseg_dev, int32_t *pix_dev,
@@ -233,27 +248,18 @@ extern "C" int fsim_render_points(fsim_t *s, float *depth_dev, int32_t *seg_dev,
   if (!xyz_dev || !pseg_dev || !count_dev || (p.n_points > 0 && !pix_dev)) FAIL(FSIM_EINVAL, "fsim_render_points: a NULL output");
   HIPCHK(hipSetDevice(s->device));
   const size_t nimg = (size_t)s->n_envs * npix;
-  if ((!depth_dev || !seg_dev) && p.cap_img < nimg) { // scratch, allocated on first use and grown with the image size
-    HIPCHK(hipStreamSynchronize(s->stream));
-    hipFree(p.d_depth); hipFree(p.d_seg);
-    p.d_depth = nullptr; p.d_seg = nullptr; p.cap_img = 0;
-    HIPCHK(hipMalloc(&p.d_depth, nimg * 4));
-    HIPCHK(hipMalloc(&p.d_seg, nimg * 4));
-    p.cap_img = nimg;
-  }
-  if (p.n_points > 0 && p.cap_cand < nimg) {
+  if (p.n_points > 0 && p.cap_cand < nimg) { // scratch, allocated on first use and grown with the image size
     HIPCHK(hipStreamSynchronize(s->stream));
     hipFree(p.d_cand);
     p.d_cand = nullptr; p.cap_cand = 0;
     HIPCHK(hipMalloc(&p.d_cand, nimg * sizeof(f4_t)));
     p.cap_cand = nimg;
   }
-  float *depth = depth_dev ? depth_dev : p.d_depth;
-  int *seg = seg_dev ? seg_dev : p.d_seg;
-  { int rc_ = fsim_render(s, depth, seg); if (rc_) return rc_; } // settles, then k_cam_pose + k_cam_ray
+  const float *depth;
+  const int *seg;
+  { int rc_ = cam_render_images(s, depth_dev, seg_dev, &depth, &seg); if (rc_) return rc_; }
   PtsGatherArgs ga{};
-  ga.ncam = k.ncam; ga.W = k.W; ga.H = k.H; ga.npix = (int)npix; ga.ncg = s->m.ncg; ga.pstride = k.pstride; ga.dense = p.n_points == 0;
-  for (int i = 0; i < FSIM_CAM_MAX; i++) ga.slope[i] = k.slope[i];
+  ga.v = cam_view(s); ga.dense = p.n_points == 0;
   for (int i = 0; i < 3; i++) { ga.lo[i] = p.lo[i]; ga.hi[i] = p.hi[i]; }
   hipLaunchKernelGGL(k_pts_gather, dim3(s->n_envs), dim3(PTS_GTHREADS), 0, s->stream, ga, k.d_pose, depth, seg, p.d_keep,
                      ga.dense ? xyz_dev : nullptr, ga.dense ? pseg_dev : nullptr, p.d_cand, count_dev);

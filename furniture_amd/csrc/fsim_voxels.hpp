@@ -1,6 +1,7 @@
 // fsim_voxels.hpp -- voxel-grid observations binned from the cameras (include/fsim_voxels.h).  Included at the end of fsim.hip, after
-// fsim_points.hpp: the host part runs fsim_render (k_cam_pose, k_cam_ray, as they are) and reads the camera poses k_cam_pose leaves in
-// the handle's pose scratch; the kernel back-projects through pts_point, the function k_pts_gather calls.
+// fsim_points.hpp: the host part renders through cam_render_images (fsim_render: k_cam_pose, k_cam_ray, as they are); the kernel stages
+// the camera poses with cam_stage_views, back-projects through pts_point and keeps a pixel by pts_seg_kept and pts_in_box, the
+// functions k_pts_gather calls.
 //
 // After fsim_render's two launches, on the same stream:
 //   k_vox_bin  one 1024-thread workgroup per (env, chunk of up to VOX_CHUNK cells).  The chunk's cells live in LDS as a 32-bit count and
@@ -17,9 +18,8 @@
 #define VOX_EMPTY 0x7fffffffu // smallest pix of a cell no pixel has reached
 
 struct VoxArgs {
-  int ncam, W, H, npix /* ncam * W * H */, ncg, pstride;
+  CamView v;
   int dx, dy, dz, ncells, nchunk, vec /* 128-bit stores: ncells % 8 == 0 and both outputs 16-B aligned */;
-  float slope[FSIM_CAM_MAX];
   float lo[3], hi[3], sc[3]; // the box and s_a = dims_a / (hi_a - lo_a), rounded once on the host
 };
 
@@ -41,20 +41,17 @@ __global__ __launch_bounds__(VOX_THREADS) void k_vox_bin(VoxArgs a, const float 
   const int e = blockIdx.x / a.nchunk, chunk = blockIdx.x - e * a.nchunk, tid = threadIdx.x;
   const int c0 = chunk * VOX_CHUNK, len = min(VOX_CHUNK, a.ncells - c0);
   unsigned *cnt = vox_lds, *mp = vox_lds + len;
-  const float *P = pose + (size_t)e * a.pstride + CAM_PW * a.ncg; // the camera rows of the env's pose scratch
-  for (int i = tid; i < CAM_PW * a.ncam; i += VOX_THREADS) cpose[i] = P[i];
-  if (tid < FSIM_CAM_MAX) cslope[tid] = a.slope[tid];
+  cam_stage_views(cpose, cslope, pose + (size_t)e * a.v.pstride + CAM_PW * a.v.ncg, a.v, tid, VOX_THREADS);
   for (int i = tid; i < len; i += VOX_THREADS) {
     cnt[i] = 0u;
     mp[i] = VOX_EMPTY;
   }
   __syncthreads();
-  const size_t base = (size_t)e * a.npix;
-  for (int p = tid; p < a.npix; p += VOX_THREADS) {
-    const int g = seg[base + p];
-    if (g < 0 || !keep[g]) continue;
-    const V3 q = pts_point(cpose, cslope, a.W, a.H, p, depth[base + p]);
-    if (!(q.x >= a.lo[0] && q.y >= a.lo[1] && q.z >= a.lo[2] && q.x <= a.hi[0] && q.y <= a.hi[1] && q.z <= a.hi[2])) continue;
+  const size_t base = (size_t)e * a.v.npix;
+  for (int p = tid; p < a.v.npix; p += VOX_THREADS) {
+    if (!pts_seg_kept(seg[base + p], keep)) continue;
+    const V3 q = pts_point(cpose, cslope, a.v.W, a.v.H, p, depth[base + p]);
+    if (!pts_in_box(q, a.lo, a.hi)) continue;
     const int c = (vox_axis(q.x, a.lo[0], a.sc[0], a.dx) * a.dy + vox_axis(q.y, a.lo[1], a.sc[1], a.dy)) * a.dz +
                   vox_axis(q.z, a.lo[2], a.sc[2], a.dz) - c0;
     if ((unsigned)c < (unsigned)len) {
@@ -92,14 +89,12 @@ __global__ __launch_bounds__(VOX_THREADS) void k_vox_bin(VoxArgs a, const float 
 struct VoxState {
   int dims[3] = {0, 0, 0}, ncells = 0;
   float lo[3], hi[3], sc[3];
-  unsigned char *d_keep = nullptr;                // [ngeom]
-  float *d_depth = nullptr; int *d_seg = nullptr; // image scratch (a NULL depth / seg of fsim_render_voxels), [n_envs * npix]
-  size_t cap_img = 0;                             // elements allocated
+  unsigned char *d_keep = nullptr; // [ngeom]
 };
 
 static void vox_free(fsim *s) {
   if (!s->vox) return;
-  hipFree(s->vox->d_keep); hipFree(s->vox->d_depth); hipFree(s->vox->d_seg);
+  hipFree(s->vox->d_keep);
   delete s->vox;
   s->vox = nullptr;
 }
@@ -114,8 +109,7 @@ extern "C" int fsim_set_voxels(fsim_t *s, const int32_t dims[3], const float box
     cells *= dims[i];
   }
   if (cells > FSIM_VOX_MAX_CELLS) FAIL(FSIM_EINVAL, "fsim_set_voxels: %d x %d x %d = %ld cells (at most %d)", dims[0], dims[1], dims[2], cells, FSIM_VOX_MAX_CELLS);
-  for (int i = 0; i < 6; i++)
-    if (!std::isfinite(box[i])) FAIL(FSIM_EINVAL, "fsim_set_voxels: box bound %d is not finite", i);
+  if (pts_box_finite("fsim_set_voxels", box)) return FSIM_EINVAL;
   float sc[3];
   for (int i = 0; i < 3; i++) {
     if (!(box[i] < box[3 + i])) FAIL(FSIM_EINVAL, "fsim_set_voxels: box lo %g >= hi %g on axis %d", box[i], box[3 + i], i);
@@ -124,15 +118,11 @@ extern "C" int fsim_set_voxels(fsim_t *s, const int32_t dims[3], const float box
     if (!std::isfinite(ext) || !std::isnormal(sc[i]))
       FAIL(FSIM_EINVAL, "fsim_set_voxels: box extent %g on axis %d gives the scale %g (not a finite normal fp32)", ext, i, sc[i]);
   }
-  std::vector<unsigned char> keep(std::max(s->ngeom, 1), 1);
-  if (geom_keep)
-    for (int g = 0; g < s->ngeom; g++) keep[g] = geom_keep[g] ? 1 : 0;
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipStreamSynchronize(s->stream)); // (a render in flight still reads the old keep table)
   if (!s->vox) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_vox_bin), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * VOX_CHUNK));
     s->vox = new VoxState();
-    HIPCHK(hipMalloc(&s->vox->d_keep, keep.size()));
   }
   VoxState &v = *s->vox;
   for (int i = 0; i < 3; i++) {
@@ -142,8 +132,7 @@ extern "C" int fsim_set_voxels(fsim_t *s, const int32_t dims[3], const float box
     v.sc[i] = sc[i];
   }
   v.ncells = (int)cells;
-  HIPCHK(hipMemcpy(v.d_keep, keep.data(), keep.size(), hipMemcpyHostToDevice));
-  return FSIM_OK;
+  return pts_upload_keep(s, geom_keep, &v.d_keep);
 }
 
 extern "C" int fsim_render_voxels(fsim_t *s, float *depth_dev, int32_t *seg_dev, int16_t *count_dev, int16_t *label_dev) {
@@ -153,28 +142,17 @@ extern "C" int fsim_render_voxels(fsim_t *s, float *depth_dev, int32_t *seg_dev,
   if (!count_dev || !label_dev) FAIL(FSIM_EINVAL, "fsim_render_voxels: a NULL output");
   VoxState &v = *s->vox;
   const CamState &k = *s->cam;
-  const long npix = (long)k.ncam * k.W * k.H;
   const int nchunk = (v.ncells + VOX_CHUNK - 1) / VOX_CHUNK;
   const size_t nblk = (size_t)s->n_envs * nchunk;
   if (nblk > 0x7fffffff) FAIL(FSIM_EINVAL, "fsim_render_voxels: %zu workgroups", nblk);
   HIPCHK(hipSetDevice(s->device));
-  const size_t nimg = (size_t)s->n_envs * npix;
-  if ((!depth_dev || !seg_dev) && v.cap_img < nimg) { // scratch, allocated on first use and grown with the image size
-    HIPCHK(hipStreamSynchronize(s->stream));
-    hipFree(v.d_depth); hipFree(v.d_seg);
-    v.d_depth = nullptr; v.d_seg = nullptr; v.cap_img = 0;
-    HIPCHK(hipMalloc(&v.d_depth, nimg * 4));
-    HIPCHK(hipMalloc(&v.d_seg, nimg * 4));
-    v.cap_img = nimg;
-  }
-  float *depth = depth_dev ? depth_dev : v.d_depth;
-  int *seg = seg_dev ? seg_dev : v.d_seg;
-  { int rc_ = fsim_render(s, depth, seg); if (rc_) return rc_; } // settles, then k_cam_pose + k_cam_ray
+  const float *depth;
+  const int *seg;
+  { int rc_ = cam_render_images(s, depth_dev, seg_dev, &depth, &seg); if (rc_) return rc_; }
   VoxArgs va{};
-  va.ncam = k.ncam; va.W = k.W; va.H = k.H; va.npix = (int)npix; va.ncg = s->m.ncg; va.pstride = k.pstride;
+  va.v = cam_view(s);
   va.dx = v.dims[0]; va.dy = v.dims[1]; va.dz = v.dims[2]; va.ncells = v.ncells; va.nchunk = nchunk;
   va.vec = v.ncells % 8 == 0 && (reinterpret_cast<uintptr_t>(count_dev) & 15) == 0 && (reinterpret_cast<uintptr_t>(label_dev) & 15) == 0;
-  for (int i = 0; i < FSIM_CAM_MAX; i++) va.slope[i] = k.slope[i];
   for (int i = 0; i < 3; i++) { va.lo[i] = v.lo[i]; va.hi[i] = v.hi[i]; va.sc[i] = v.sc[i]; }
   const size_t lds = 8 * (size_t)std::min(v.ncells, VOX_CHUNK);
   hipLaunchKernelGGL(k_vox_bin, dim3((unsigned)nblk), dim3(VOX_THREADS), lds, s->stream, va, k.d_pose, depth, seg, v.d_keep, count_dev, label_dev);

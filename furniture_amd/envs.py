@@ -493,24 +493,18 @@ class FurnitureBatchEnv:
             self.sim.set_cameras(self.cameras)
             shape = (num_envs, len(self.cameras), self.cameras[0].height, self.cameras[0].width)
             self._cam_out = (torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.int32, device=dev))
-        self.point_cloud = point_cloud
-        if point_cloud is not None:  # (without it: no allocation, no launch, the same observation dict)
-            self.sim.set_points(point_cloud)
-            self._pts_out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
-            for k, (sh, dt) in self.sim.points_shapes().items():
-                self._pts_out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
-        self.voxels = voxels
-        if voxels is not None:  # (without it: no allocation, no launch, the same observation dict)
-            self.sim.set_voxels(voxels)
-            self._vox_out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
-            for k, (sh, dt) in self.sim.voxels_shapes().items():
-                self._vox_out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
-        self.normals = normals
-        if normals is not None:  # (without it: no allocation, no launch, the same observation dict)
-            self.sim.set_normals(normals)
-            self._nrm_out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
-            for k, (sh, dt) in self.sim.normals_shapes().items():
-                self._nrm_out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
+        self.point_cloud, self.voxels, self.normals = point_cloud, voxels, normals
+        # the settings and the output tensors of each derived observation asked for (without it: no allocation, no launch, the same
+        # observation dict); all of them render their images into _cam_out
+        for spec, set_spec, shapes, bufs in ((point_cloud, self.sim.set_points, self.sim.points_shapes, "_pts_out"),
+                                             (voxels, self.sim.set_voxels, self.sim.voxels_shapes, "_vox_out"),
+                                             (normals, self.sim.set_normals, self.sim.normals_shapes, "_nrm_out")):
+            if spec is not None:
+                set_spec(spec)
+                out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
+                for k, (sh, dt) in shapes().items():
+                    out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
+                setattr(self, bufs, out)
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property

@@ -467,7 +467,7 @@ class FSim:
             raise FsimError("render: no cameras set (FSim.set_cameras)")
         if not (depth or segmentation):
             raise ValueError("render: neither depth nor segmentation asked for")
-        shape = (self.n_envs, len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+        shape = (self.n_envs,) + self._image_shape()
         d, s = out if out is not None else (None, None)
         if depth and d is None:
             d = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -481,6 +481,30 @@ class FSim:
         self._chk(lib().fsim_render(self._h, d.data_ptr() if d is not None else None, s.data_ptr() if s is not None else None))
         cur.wait_stream(self.torch_stream)
         return d, s
+
+    def _image_shape(self):
+        """(C, H, W) of one env's images"""
+        return (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+
+    def _render_derived(self, name, fn, keys, want, images, out):
+        """The part render_points / render_voxels / render_normals share.  want: {key: (shape, dtype)} of the outputs (without the n_envs
+        dimension), to which images=True adds the two images; out: a dict of tensors to write into (a missing key: a new tensor).  Calls
+        fn(handle, depth, segmentation, *keys' tensors), NULL for a key that is not in want -> dict of tensors."""
+        torch = self.torch
+        if images:
+            want = dict(want, camera_depth=(self._image_shape(), torch.float32), camera_segmentation=(self._image_shape(), torch.int32))
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out.get(k) if out is not None else None
+            if t is None:
+                t = torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "%s: out[%r] of the wrong shape / type" % (name, k)
+            res[k] = t
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(fn(self._h, *[res[k].data_ptr() if k in res else None for k in ("camera_depth", "camera_segmentation") + keys]))
+        cur.wait_stream(self.torch_stream)
+        return res
 
     # -- point clouds from the cameras (include/fsim_points.h, furniture_amd/points.py) ------------------------------------------
     points = None
@@ -498,9 +522,8 @@ class FSim:
     def points_shapes(self):
         """{key: (shape, dtype)} of render_points' outputs (without the n_envs dimension); dense mode has no point_cloud_pixel"""
         torch = self.torch
-        C, H, W = len(self.cameras), self.cameras[0].height, self.cameras[0].width
         n = self.points.n_points
-        per = (C, H, W) if n == 0 else (n,)
+        per = self._image_shape() if n == 0 else (n,)
         out = {"point_cloud": (per + (3,), torch.float32), "point_cloud_segmentation": (per, torch.int32), "point_cloud_count": ((), torch.int32)}
         if n > 0:
             out["point_cloud_pixel"] = ((n,), torch.int32)
@@ -512,29 +535,12 @@ class FSim:
         the kept pixels), in sampled mode point_cloud_pixel (int32 cam*H*W + row*W + col, -1 = none), and with images=True camera_depth /
         camera_segmentation [n, C, H, W] as FSim.render gives them.  out: a dict of such tensors to write into instead of new ones.
         Ordered with torch's current stream both ways."""
-        torch = self.torch
         if self.points is None:
             raise FsimError("render_points: no point-cloud settings (FSim.set_points)")
         if not self.cameras:
             raise FsimError("render_points: no cameras set (FSim.set_cameras)")
-        want = self.points_shapes()
-        if images:
-            img = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
-            want["camera_depth"], want["camera_segmentation"] = (img, torch.float32), (img, torch.int32)
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out.get(k) if out is not None else None
-            if t is None:
-                t = torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "render_points: out[%r] of the wrong shape / type" % k
-            res[k] = t
-        ptr = lambda k: res[k].data_ptr() if k in res else None
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_render_points(self._h, ptr("camera_depth"), ptr("camera_segmentation"), ptr("point_cloud"),
-                                           ptr("point_cloud_segmentation"), ptr("point_cloud_pixel"), ptr("point_cloud_count")))
-        cur.wait_stream(self.torch_stream)
-        return res
+        return self._render_derived("render_points", lib().fsim_render_points, ("point_cloud", "point_cloud_segmentation", "point_cloud_pixel",
+                                                                                "point_cloud_count"), self.points_shapes(), images, out)
 
     # -- voxel grids from the cameras (include/fsim_voxels.h, furniture_amd/voxels.py) ----------------------------------------------
     voxels = None
@@ -562,29 +568,11 @@ class FSim:
         (int16 model geom id of the cell's first kept pixel in (camera, row, column) order, -1 = empty), and with images=True
         camera_depth / camera_segmentation [n, C, H, W] as FSim.render gives them.  out: a dict of such tensors to write into instead of
         new ones.  Ordered with torch's current stream both ways."""
-        torch = self.torch
         if self.voxels is None:
             raise FsimError("render_voxels: no voxel settings (FSim.set_voxels)")
         if not self.cameras:
             raise FsimError("render_voxels: no cameras set (FSim.set_cameras)")
-        want = self.voxels_shapes()
-        if images:
-            img = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
-            want["camera_depth"], want["camera_segmentation"] = (img, torch.float32), (img, torch.int32)
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out.get(k) if out is not None else None
-            if t is None:
-                t = torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "render_voxels: out[%r] of the wrong shape / type" % k
-            res[k] = t
-        ptr = lambda k: res[k].data_ptr() if k in res else None
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_render_voxels(self._h, ptr("camera_depth"), ptr("camera_segmentation"), ptr("voxel_count"),
-                                           ptr("voxel_segmentation")))
-        cur.wait_stream(self.torch_stream)
-        return res
+        return self._render_derived("render_voxels", lib().fsim_render_voxels, ("voxel_count", "voxel_segmentation"), self.voxels_shapes(), images, out)
 
     # -- normal / shaded images from the cameras (include/fsim_normals.h, furniture_amd/normals.py) ----------------------------------
     normals = None
@@ -602,7 +590,7 @@ class FSim:
     def normals_shapes(self):
         """{key: (shape, dtype)} of render_normals' outputs (without the n_envs dimension)"""
         torch = self.torch
-        img = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
+        img = self._image_shape()
         out = {}
         if self.normals.normal:
             out["camera_normal"] = (img + (3,), torch.float32)
@@ -616,28 +604,11 @@ class FSim:
         sees, (0, 0, 0) where it sees nothing) and / or camera_shaded (uint8 [n, C, H, W, 4], RGBA), as the settings ask, and with
         images=True camera_depth / camera_segmentation [n, C, H, W] as FSim.render gives them.  out: a dict of such tensors to write
         into instead of new ones.  Ordered with torch's current stream both ways."""
-        torch = self.torch
         if self.normals is None:
             raise FsimError("render_normals: no normals settings (FSim.set_normals)")
         if not self.cameras:
             raise FsimError("render_normals: no cameras set (FSim.set_cameras)")
-        want = self.normals_shapes()
-        if images:
-            img = (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
-            want["camera_depth"], want["camera_segmentation"] = (img, torch.float32), (img, torch.int32)
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out.get(k) if out is not None else None
-            if t is None:
-                t = torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "render_normals: out[%r] of the wrong shape / type" % k
-            res[k] = t
-        ptr = lambda k: res[k].data_ptr() if k in res else None
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_render_normals(self._h, ptr("camera_depth"), ptr("camera_segmentation"), ptr("camera_normal"), ptr("camera_shaded")))
-        cur.wait_stream(self.torch_stream)
-        return res
+        return self._render_derived("render_normals", lib().fsim_render_normals, ("camera_normal", "camera_shaded"), self.normals_shapes(), images, out)
 
     def kernel_time_ms(self):
         ms, n = ctypes.c_double(), ctypes.c_int32()

@@ -21,11 +21,16 @@ W, H = 64, 48
 _POISON = os.environ.get("FSIM_TEST_POISON")
 
 
-def _render(sim, **kw):
+def _poison():
+    """FSIM_TEST_POISON=<hex>: fill every CU's LDS with the pattern (called before a render)"""
     if _POISON:
         tool = ctypes.CDLL(os.path.join(ROOT, "tests", "liblds_poison.so"))
         for _ in range(2):
             assert tool.lds_poison(ctypes.c_uint(int(_POISON, 16))) == 0
+
+
+def _render(sim, **kw):
+    _poison()
     d, s = sim.render(**kw)
     torch.cuda.synchronize()
     return d, s
@@ -58,14 +63,14 @@ def _steps(sim, k, seed=5):
         sim.sync()
 
 
-def _cameras(m, qpos, attach):
+def _cameras(m, qpos, attach, w=W, h=H):
     parts = np.stack([qpos[int(a):int(a) + 3] for a in m.part_qposadr])
     c = parts.mean(0)
-    world = Camera(c + np.array([1.1, -0.9, 0.9]), lookat=c, fovy=50, width=W, height=H, znear=0.02, zfar=6.0)
+    world = Camera(c + np.array([1.1, -0.9, 0.9]), lookat=c, fovy=50, width=w, height=h, znear=0.02, zfar=6.0)
     if attach == "cursor0":  # the cursor box from 0.3 m above, looking straight down
-        cam = Camera((0.0, 0.0, 0.3), fovy=70, width=W, height=H, znear=0.02, zfar=6.0, body=attach)
+        cam = Camera((0.0, 0.0, 0.3), fovy=70, width=w, height=h, znear=0.02, zfar=6.0, body=attach)
     else:  # wrist camera behind the hand, looking along the gripper
-        cam = Camera((0.0, 0.05, -0.05), quat=(0.0, 1.0, 0.0, 0.0), fovy=80, width=W, height=H, znear=0.02, zfar=6.0, body=attach)
+        cam = Camera((0.0, 0.05, -0.05), quat=(0.0, 1.0, 0.0, 0.0), fovy=80, width=w, height=h, znear=0.02, zfar=6.0, body=attach)
     return [world, cam]
 
 

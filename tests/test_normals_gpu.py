@@ -8,9 +8,6 @@ with an ambiguity margin (normals_reference) of at least 5e-4 m -- the hit point
 the other face may legitimately win -- and on a flat face or a curved one of radius at least 5 mm.  At most 15 % of an image's hit
 pixels may be left out.  Flat pixels: every component within 1e-5 (the normal is a column of the geom's rotation; the device's
 kinematics agree with the oracle's to 2e-6).  Curved pixels: the angle to the reference is at most CURVED_TOL."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -20,15 +17,14 @@ from furniture_amd.envs import make_config
 from furniture_amd.normals import Normals, default_palette
 from furniture_amd.points import PointCloud
 from furniture_amd.sim import INFO_DIM, FSim, FsimError, lib
+from furniture_amd.voxels import VoxelGrid
 from oracle.oracle_sim import OracleSim
 from tests import camera_reference as cref
 from tests import normals_reference as nref
-from tests.test_camera_gpu import _make, _steps
+from tests.test_camera_gpu import _cameras, _make, _poison, _steps
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H = 64, 48  # 3072 pixels: two chunks of the normal pass, the second one half full
-_POISON = os.environ.get("FSIM_TEST_POISON")
 MARGIN, MIN_RADIUS, LEFT_OUT, FLAT_TOL = 5e-4, 5e-3, 0.15, 1e-5
 # curved surfaces (sphere, capsule, cylinder side): the normal turns by (error of the hit point) / radius.  The tolerance is 4 x the
 # largest angle measured on an MI355X over the cases of this file, and never above 1e-2 rad
@@ -37,25 +33,10 @@ BOTH = Normals(normal=True, shaded=True, ambient=0.25, background=(30, 30, 40, 2
 
 
 def _render(sim, **kw):
-    if _POISON:
-        tool = ctypes.CDLL(os.path.join(ROOT, "tests", "liblds_poison.so"))
-        for _ in range(2):
-            assert tool.lds_poison(ctypes.c_uint(int(_POISON, 16))) == 0
+    _poison()
     res = sim.render_normals(**kw)
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in res.items()}
-
-
-def _cameras(m, qpos, attach, w=W, h=H):
-    """the two cameras of tests/test_camera_gpu.py (restated): a world camera looking at the parts and a wrist / cursor camera"""
-    parts = np.stack([qpos[int(a):int(a) + 3] for a in m.part_qposadr])
-    c = parts.mean(0)
-    world = Camera(c + np.array([1.1, -0.9, 0.9]), lookat=c, fovy=50, width=w, height=h, znear=0.02, zfar=6.0)
-    if attach == "cursor0":  # the cursor box from 0.3 m above, looking straight down
-        cam = Camera((0.0, 0.0, 0.3), fovy=70, width=w, height=h, znear=0.02, zfar=6.0, body=attach)
-    else:  # wrist camera behind the hand, looking along the gripper
-        cam = Camera((0.0, 0.05, -0.05), quat=(0.0, 1.0, 0.0, 0.0), fovy=80, width=w, height=h, znear=0.02, zfar=6.0, body=attach)
-    return [world, cam]
 
 
 def _shade(normal, seg, depth, cam_pos, cam_R, cam, spec, palette):
@@ -216,6 +197,32 @@ def test_one_output_at_a_time():
     pal, seg = default_palette(m), flat["camera_segmentation"]
     assert (flat["camera_shaded"][seg >= 0] == pal[seg[seg >= 0]]).all()  # ambient 1: the palette's colour itself
     assert (flat["camera_shaded"][seg < 0] == (1, 2, 3, 4)).all()
+    sim.close()
+
+
+def test_one_image_scratch_serves_points_voxels_and_normals():
+    """With images=False the three calls render into the one image scratch the handle owns, and a larger camera set needs a larger one:
+    each result is, byte for byte, that of the same call with images=True (the caller's images, no scratch) made right after it."""
+    m, sim = _make("Sawyer", "table_lack_0825", 2)
+    _steps(sim, 2)
+    q0 = sim.get_state("qpos")["qpos"][0].cpu().numpy()
+    c = np.stack([q0[int(a):int(a) + 3] for a in m.part_qposadr]).mean(0)
+    sim.set_points(PointCloud(0))
+    sim.set_voxels(VoxelGrid((17, 9, 5), (c - 0.8, c + 0.8)))
+    sim.set_normals(BOTH)
+    calls = {"points": sim.render_points, "voxels": sim.render_voxels, "normals": sim.render_normals}
+    compared = 0
+    for (w, h), order in (((33, 17), ("points", "voxels", "normals")), ((64, 48), ("normals", "points", "voxels"))):
+        sim.set_cameras(_cameras(m, q0, "right_hand", w, h))
+        for name in order:
+            _poison()
+            got = {k: v.cpu().numpy() for k, v in calls[name](images=False).items()}
+            want = {k: v.cpu().numpy() for k, v in calls[name](images=True).items()}
+            assert sorted(want) == sorted(list(got) + ["camera_depth", "camera_segmentation"]), (w, h, name)
+            for k in got:
+                assert got[k].tobytes() == want[k].tobytes(), (w, h, name, k)
+                compared += 1
+    assert compared == 2 * (3 + 2 + 2)  # point_cloud, _segmentation, _count; voxel_count, _segmentation; camera_normal, _shaded
     sim.close()
 
 
