@@ -509,6 +509,7 @@ struct CamState; // fsim_camera.hpp
 struct PtsState; // fsim_points.hpp
 struct VoxState; // fsim_voxels.hpp
 struct NrmState; // fsim_normals.hpp
+struct FlwState; // fsim_flow.hpp
 struct KernelSet { const char *name; PhysicsFn physics; EnvStepFn env_step; PhysicsFn physics_mw; EnvStepFn env_step_mw; EnvStepXFn env_step_x; };
 enum { MW_OFF = 0, MW_RULE = 1, MW_ALL = 2 }; // fsim::mw_mode
 
@@ -590,6 +591,7 @@ struct fsim {
   PtsState *pts = nullptr; // point-cloud settings and scratch (fsim_set_points): nothing is allocated or launched without them
   VoxState *vox = nullptr; // voxel-grid settings and scratch (fsim_set_voxels): nothing is allocated or launched without them
   NrmState *nrm = nullptr; // normal / shaded image settings and scratch (fsim_set_normals): nothing is allocated or launched without them
+  FlwState *flw = nullptr; // flow / velocity image scratch (the first fsim_render_flow): nothing is allocated or launched without that call
 };
 
 static void la_policy(fsim *s);
@@ -1004,6 +1006,7 @@ static void cam_free(fsim *s);
 static void pts_free(fsim *s);
 static void vox_free(fsim *s);
 static void nrm_free(fsim *s);
+static void flw_free(fsim *s);
 extern "C" void fsim_destroy(fsim_t *s) {
   if (!s) return;
   hipSetDevice(s->device);
@@ -1012,6 +1015,7 @@ extern "C" void fsim_destroy(fsim_t *s) {
   pts_free(s);
   vox_free(s);
   nrm_free(s);
+  flw_free(s);
   hipFree(s->d_sh_state); hipFree(s->d_sh_obs); hipFree(s->d_sh_prog); hipFree(s->d_sh_serial); hipFree(s->d_tab_serial); hipFree(s->d_sh_jobs);
   if (s->xfer) { hipStreamSynchronize(s->xfer); hipStreamDestroy(s->xfer); }
   hipFree(s->d_ly_r[0]); hipFree(s->d_ly_r[1]); hipFree(s->d_ly_r[2]); hipFree(s->d_prev); hipFree(s->d_ovf_list); hipFree(s->d_ovf_list2);
@@ -1664,3 +1668,4 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
 #include "fsim_points.hpp"
 #include "fsim_voxels.hpp"
 #include "fsim_normals.hpp"
+#include "fsim_flow.hpp"

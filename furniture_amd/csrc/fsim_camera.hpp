@@ -365,6 +365,7 @@ extern "C" int fsim_set_cameras(fsim_t *s, int n_cam, const fsim_camera_t *cams,
   { int rc_ = settle(s); if (rc_) return rc_; }
   HIPCHK(hipStreamSynchronize(s->stream)); // (a render in flight still reads the old tables)
   cam_free(s);
+  flw_free(s); // (the twist scratch of fsim_render_flow is sized by the camera set)
   s->cam = new CamState(c);
   CamState &k = *s->cam;
   HIPCHK(hipMalloc(&k.d_cams, crow.size() * 4));

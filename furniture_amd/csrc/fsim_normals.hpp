@@ -136,16 +136,24 @@ static void nrm_free(fsim *s) {
   s->nrm = nullptr;
 }
 
+// The model-geom-id -> colliding-geom table [max(ngeom, 1)] k_cam_normal and k_cam_flow (fsim_flow.hpp) stage: the row of the staged geom
+// table that shows model geom g, NRM_NOGEOM for a geom that does not collide.
+static int nrm_idtab(const fsim *s, std::vector<unsigned char> &idtab) {
+  std::vector<int> cg_orig;
+  if (!blob_i(s->blob, "cg_orig", cg_orig)) return FSIM_EINVAL;
+  idtab.assign(std::max(s->ngeom, 1), NRM_NOGEOM);
+  for (int k = 0; k < s->m.ncg; k++)
+    if (cg_orig[k] >= 0 && cg_orig[k] < s->ngeom) idtab[cg_orig[k]] = (unsigned char)k;
+  return FSIM_OK;
+}
+
 extern "C" int fsim_set_normals(fsim_t *s, const uint8_t *palette, const uint8_t background[4], float ambient) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_normals: null handle");
   if (!std::isfinite(ambient) || ambient < 0.0f || ambient > 1.0f) FAIL(FSIM_EINVAL, "fsim_set_normals: ambient %g (0 .. 1)", ambient);
   if (s->m.ncg > FSIM_CAM_MAX_GEOMS) FAIL(FSIM_EINVAL, "fsim_set_normals: %d colliding geoms (the cameras stage at most %d)", s->m.ncg, FSIM_CAM_MAX_GEOMS);
-  std::vector<int> cg_orig;
-  if (!blob_i(s->blob, "cg_orig", cg_orig)) return FSIM_EINVAL;
   const int ng = std::max(s->ngeom, 1);
-  std::vector<unsigned char> idtab(ng, NRM_NOGEOM);
-  for (int k = 0; k < s->m.ncg; k++)
-    if (cg_orig[k] >= 0 && cg_orig[k] < s->ngeom) idtab[cg_orig[k]] = (unsigned char)k;
+  std::vector<unsigned char> idtab;
+  { int rc_ = nrm_idtab(s, idtab); if (rc_) return rc_; }
   std::vector<unsigned> pal(ng, 0u);
   if (palette)
     for (int g = 0; g < s->ngeom; g++)

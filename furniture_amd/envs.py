@@ -359,9 +359,10 @@ class FurnitureBatchEnv:
     point_cloud = None
     voxels = None
     normals = None
+    flow = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -380,7 +381,13 @@ class FurnitureBatchEnv:
         ask.  With cameras and normals alone, images and normals come from one fsim_render_normals call.  With point_cloud as well, the
         observations also hold point_cloud_normal (float32, the shape of point_cloud: camera_normal gathered at the sampled pixels,
         (0, 0, 0) for padding; dense mode: camera_normal with (0, 0, 0) where point_cloud_segmentation is -1), and the cameras are
-        rendered once more (fsim_render_points, then fsim_render_normals: one more ray pass of the same state, as with voxels)."""
+        rendered once more (fsim_render_points, then fsim_render_normals: one more ray pass of the same state, as with voxels).
+        flow: a furniture_amd.flow.Flow (needs cameras) -- the observations then also hold camera_flow (float32 [n, C, H, W, 3]: the
+        exact image motion of the material point each pixel sees, columns / s to the right and rows / s downward, and its depth rate in
+        m/s) and / or camera_velocity (float32 [n, C, H, W, 3]: that point's world-frame velocity in m/s), (0, 0, 0) where a pixel sees
+        nothing, from one fsim_render_flow call after the others (one more ray pass of the same state when there are any).  With
+        point_cloud as well and velocity=True, the observations also hold point_cloud_velocity (camera_velocity gathered as
+        point_cloud_normal is)."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -390,6 +397,9 @@ class FurnitureBatchEnv:
         if normals is not None:
             from .normals import check as check_normals
             check_normals(normals, list(cameras) if cameras else None)
+        if flow is not None:
+            from .flow import check as check_flow
+            check_flow(flow, list(cameras) if cameras else None)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -493,12 +503,13 @@ class FurnitureBatchEnv:
             self.sim.set_cameras(self.cameras)
             shape = (num_envs, len(self.cameras), self.cameras[0].height, self.cameras[0].width)
             self._cam_out = (torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.int32, device=dev))
-        self.point_cloud, self.voxels, self.normals = point_cloud, voxels, normals
+        self.point_cloud, self.voxels, self.normals, self.flow = point_cloud, voxels, normals, flow
         # the settings and the output tensors of each derived observation asked for (without it: no allocation, no launch, the same
         # observation dict); all of them render their images into _cam_out
         for spec, set_spec, shapes, bufs in ((point_cloud, self.sim.set_points, self.sim.points_shapes, "_pts_out"),
                                              (voxels, self.sim.set_voxels, self.sim.voxels_shapes, "_vox_out"),
-                                             (normals, self.sim.set_normals, self.sim.normals_shapes, "_nrm_out")):
+                                             (normals, self.sim.set_normals, self.sim.normals_shapes, "_nrm_out"),
+                                             (flow, self.sim.set_flow, self.sim.flow_shapes, "_flw_out")):
             if spec is not None:
                 set_spec(spec)
                 out = {"camera_depth": self._cam_out[0], "camera_segmentation": self._cam_out[1]}
@@ -543,6 +554,13 @@ class FurnitureBatchEnv:
                 sp.append(("camera_shaded", spaces.Box(0, 255, shape=shape + (4,), dtype=np.uint8)))
             if self.normals.normal and self.point_cloud is not None:
                 sp.append(("point_cloud_normal", spaces.Box(-1.0, 1.0, shape=per + (3,), dtype=np.float32)))
+        if self.flow is not None:
+            if self.flow.flow:
+                sp.append(("camera_flow", spaces.Box(-np.inf, np.inf, shape=shape + (3,), dtype=np.float32)))
+            if self.flow.velocity:
+                sp.append(("camera_velocity", spaces.Box(-np.inf, np.inf, shape=shape + (3,), dtype=np.float32)))
+            if self.flow.velocity and self.point_cloud is not None:
+                sp.append(("point_cloud_velocity", spaces.Box(-np.inf, np.inf, shape=per + (3,), dtype=np.float32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -555,7 +573,8 @@ class FurnitureBatchEnv:
         """the observation dict of the state the last sync() left: _split of the slab, plus the camera images when cameras are set and
         the point cloud when one is set (images and points from one fsim_render_points call: one ray pass) and the voxel grid when one is
         set (from one fsim_render_voxels call; with a point cloud as well, that is a second ray pass of the same state) and the normal /
-        shaded images when they are set (from one fsim_render_normals call, after the others: one more ray pass when there are any)"""
+        shaded images when they are set (from one fsim_render_normals call, after the others: one more ray pass when there are any) and
+        the flow / velocity images when they are set (from one fsim_render_flow call, last: again one more ray pass when there are any)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -571,19 +590,26 @@ class FurnitureBatchEnv:
                 if k in res:
                     out[k] = res[k]
             if self.normals.normal and self.point_cloud is not None:
-                out["point_cloud_normal"] = self._point_normals(res["camera_normal"])
-        if self.cameras and self.point_cloud is None and self.voxels is None and self.normals is None:
+                out["point_cloud_normal"] = self._at_points(res["camera_normal"])
+        if self.flow is not None:
+            res = self.sim.render_flow(images=True, out=self._flw_out)
+            for k in ("camera_depth", "camera_segmentation", "camera_flow", "camera_velocity"):
+                if k in res:
+                    out[k] = res[k]
+            if self.flow.velocity and self.point_cloud is not None:
+                out["point_cloud_velocity"] = self._at_points(res["camera_velocity"])
+        if self.cameras and self.point_cloud is None and self.voxels is None and self.normals is None and self.flow is None:
             out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
         return out
 
-    def _point_normals(self, normal):
-        """camera_normal at the point cloud's pixels: dense mode masks the image where the dense label is -1; sampled mode gathers at
-        point_cloud_pixel ((0, 0, 0) for the padding of an env without kept pixels)"""
+    def _at_points(self, image):
+        """a per-pixel xyz image (camera_normal, camera_velocity) at the point cloud's pixels: dense mode masks the image where the dense
+        label is -1; sampled mode gathers at point_cloud_pixel ((0, 0, 0) for the padding of an env without kept pixels)"""
         torch = self.sim.torch
         if self.point_cloud.dense:
-            return torch.where((self._pts_out["point_cloud_segmentation"] >= 0).unsqueeze(-1), normal, torch.zeros_like(normal))
+            return torch.where((self._pts_out["point_cloud_segmentation"] >= 0).unsqueeze(-1), image, torch.zeros_like(image))
         pix = self._pts_out["point_cloud_pixel"]
-        got = torch.gather(normal.reshape(normal.shape[0], -1, 3), 1, pix.clamp(min=0).long().unsqueeze(-1).expand(-1, -1, 3))
+        got = torch.gather(image.reshape(image.shape[0], -1, 3), 1, pix.clamp(min=0).long().unsqueeze(-1).expand(-1, -1, 3))
         return torch.where((pix >= 0).unsqueeze(-1), got, torch.zeros_like(got))
 
     @property
@@ -918,7 +944,7 @@ class _SingleEnv:
             dev = old.sim.device.index or 0
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
-                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals)
+                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())
@@ -941,9 +967,13 @@ class _SingleEnv:
         "human") is not available: the compiled models hold no visual meshes, only the collision geometry the cameras see.
         "normal_array": the world-frame surface normals [H, W, 3] float32 of camera 0; "shaded_array": a Lambert-shaded colour-by-part
         picture [H, W, 3] uint8 of the collision geometry from camera 0 (the env's normals= settings when it has them, else the defaults
-        of furniture_amd.normals.Normals)."""
+        of furniture_amd.normals.Normals).  "flow_array": the optical flow [H, W, 3] float32 of camera 0 (columns / s, rows / s, depth
+        rate in m/s); "velocity_array": the world-frame surface velocity [H, W, 3] float32 (m/s) of what camera 0 sees (the env's flow=
+        settings when it has them, else a temporary furniture_amd.flow.Flow)."""
         if mode in ("normal_array", "shaded_array"):
             return self._render_normals(mode)
+        if mode in ("flow_array", "velocity_array"):
+            return self._render_flow(mode)
         if mode != "depth_array":
             raise NotImplementedError("render(%r): RGB rendering needs the reference's visual meshes (not part of the compiled model) and "
                                       "the Unity / MuJoCo viewer, both outside the accelerated hot path; render('depth_array') gives the "
@@ -974,6 +1004,20 @@ class _SingleEnv:
                 else:  # (the handle keeps the temporary settings, unused: FSim.render_normals refuses without FSim.normals, and an env
                     sim.normals = None  # without normals= never calls it; the next render("..._array") sets them again)
         return img if mode == "normal_array" else np.ascontiguousarray(img[:, :, :3])
+
+    def _render_flow(self, mode):
+        from .flow import Flow
+        if not self._b.cameras:
+            raise ValueError("render(%r) needs cameras: make the env with cameras=[furniture_amd.camera.Camera(...)]" % mode)
+        sim, key = self._b.sim, "camera_flow" if mode == "flow_array" else "camera_velocity"
+        sim.sync()
+        keep = sim.flow
+        if keep is None or not (keep.flow if mode == "flow_array" else keep.velocity):
+            sim.set_flow(Flow(flow=mode == "flow_array", velocity=mode == "velocity_array"))
+        try:
+            return sim.render_flow()[key][0, 0].cpu().numpy()
+        finally:
+            sim.flow = keep  # the env's own settings (its observation buffers are sized for them), or none
 
     def close(self):
         self._b.close()

@@ -50,6 +50,9 @@ class FurnitureMixedBatchEnv:
         if kw.pop("normals", None) is not None:
             raise NotImplementedError("normals= is not supported by the mixed-furniture batch (one camera set per FurnitureBatchEnv): "
                                       "make one FurnitureBatchEnv per furniture instead")
+        if kw.pop("flow", None) is not None:
+            raise NotImplementedError("flow= is not supported by the mixed-furniture batch (one camera set per FurnitureBatchEnv): "
+                                      "make one FurnitureBatchEnv per furniture instead")
         cfg = config if config is not None else make_config()
         for key, v in kw.items():
             setattr(cfg, key, v)

@@ -62,7 +62,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -167,6 +167,7 @@ def lib():
         L.fsim_render_voxels.argtypes = [ctypes.c_void_p] * 5
         L.fsim_set_normals.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float]
         L.fsim_render_normals.argtypes = [ctypes.c_void_p] * 5
+        L.fsim_render_flow.argtypes = [ctypes.c_void_p] * 5
         _LIB = L
     return _LIB
 
@@ -188,6 +189,8 @@ POINTS_SYMBOLS = ["fsim_set_points", "fsim_render_points"]
 VOXELS_SYMBOLS = ["fsim_set_voxels", "fsim_render_voxels"]
 # the normal / shaded image entry points: a header of their own (include/fsim_normals.h), exported by the same library
 NORMALS_SYMBOLS = ["fsim_set_normals", "fsim_render_normals"]
+# the flow / velocity image entry point: a header of its own (include/fsim_flow.h), exported by the same library
+FLOW_SYMBOLS = ["fsim_render_flow"]
 
 
 def preassembled_rows(model, preassembled):
@@ -487,7 +490,7 @@ class FSim:
         return (len(self.cameras), self.cameras[0].height, self.cameras[0].width)
 
     def _render_derived(self, name, fn, keys, want, images, out):
-        """The part render_points / render_voxels / render_normals share.  want: {key: (shape, dtype)} of the outputs (without the n_envs
+        """The part render_points / render_voxels / render_normals / render_flow share.  want: {key: (shape, dtype)} of the outputs (without the n_envs
         dimension), to which images=True adds the two images; out: a dict of tensors to write into (a missing key: a new tensor).  Calls
         fn(handle, depth, segmentation, *keys' tensors), NULL for a key that is not in want -> dict of tensors."""
         torch = self.torch
@@ -609,6 +612,40 @@ class FSim:
         if not self.cameras:
             raise FsimError("render_normals: no cameras set (FSim.set_cameras)")
         return self._render_derived("render_normals", lib().fsim_render_normals, ("camera_normal", "camera_shaded"), self.normals_shapes(), images, out)
+
+    # -- flow / velocity images from the cameras (include/fsim_flow.h, furniture_amd/flow.py) ------------------------------------------
+    flow = None
+
+    def set_flow(self, spec):
+        """Set the flow / velocity image settings (a furniture_amd.flow.Flow).  Host only: the library has no settings for them."""
+        from .flow import Flow
+        if not isinstance(spec, Flow):
+            raise TypeError("set_flow: a furniture_amd.flow.Flow, not %r" % type(spec).__name__)
+        self.flow = spec
+
+    def flow_shapes(self):
+        """{key: (shape, dtype)} of render_flow's outputs (without the n_envs dimension)"""
+        torch = self.torch
+        img = self._image_shape()
+        out = {}
+        if self.flow.flow:
+            out["camera_flow"] = (img + (3,), torch.float32)
+        if self.flow.velocity:
+            out["camera_velocity"] = (img + (3,), torch.float32)
+        return out
+
+    def render_flow(self, images=False, out=None):
+        """Render the cameras once and derive the flow and / or velocity image (include/fsim_flow.h), for the state sync() leaves -> dict
+        of device tensors: camera_flow (float32 [n, C, H, W, 3]: columns / s to the right, rows / s downward, depth rate in m/s of the
+        material point the pixel sees) and / or camera_velocity (float32 [n, C, H, W, 3]: that point's world-frame velocity in m/s), as the
+        settings ask, (0, 0, 0) where the pixel sees nothing, and with images=True camera_depth / camera_segmentation [n, C, H, W] as
+        FSim.render gives them.  out: a dict of such tensors to write into instead of new ones.  Ordered with torch's current stream both
+        ways."""
+        if self.flow is None:
+            raise FsimError("render_flow: no flow settings (FSim.set_flow)")
+        if not self.cameras:
+            raise FsimError("render_flow: no cameras set (FSim.set_cameras)")
+        return self._render_derived("render_flow", lib().fsim_render_flow, ("camera_flow", "camera_velocity"), self.flow_shapes(), images, out)
 
     def kernel_time_ms(self):
         ms, n = ctypes.c_double(), ctypes.c_int32()

@@ -1,0 +1,88 @@
+"""Time fsim_render_flow (include/fsim_flow.h): Sawyer + table_lack_0825, 4096 envs (first argument) after a reset and three random
+steps.  Cases: one world camera and world + wrist camera, 64 x 64 each, and one 128 x 128 world camera; flow and velocity image both,
+then each alone.  HIP events around calls on the handle's stream, median of the repeats (second argument, 20):
+  rays    = fsim_render alone (k_cam_pose + k_cam_ray);
+  flow    = fsim_render_flow minus rays (k_cam_twist + k_cam_flow);
+  normals = fsim_render_normals (the normal image alone) minus rays (k_cam_normal), the yardstick of the same session;
+  total   = fsim_render_flow.
+The bytes bound of the flow pass: depth and segmentation read once (8 B per pixel) and each output written once (12 B per pixel), over
+the 8 TB/s HBM peak.  One JSON line per case."""
+import json, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from furniture_amd.camera import Camera
+from furniture_amd.envs import ResetTableSampler, make_config
+from furniture_amd.flow import Flow
+from furniture_amd.mjcf.model import load_compiled
+from furniture_amd.normals import Normals
+from furniture_amd.sim import INFO_DIM, FSim, default_config
+
+HBM_BYTES_PER_S = 8.0e12  # MI355X HBM3E peak
+
+n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+m = load_compiled("Sawyer", "table_lack_0825")
+ecfg = make_config(unity=False, record_vid=False, furniture_name="table_lack_0825", seed=7)
+cfg = default_config()
+cfg.auto_reset = 0
+sim = FSim(m, n, config=cfg)
+p, nz = ResetTableSampler(m, ecfg, 7, 0, n).draw()
+sim.set_reset_tables(p, nz)
+dev = sim.device
+obs, rew = torch.zeros((n, sim.obs_dim), device=dev), torch.zeros(n, device=dev)
+done, info = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros((n, INFO_DIM), dtype=torch.int32, device=dev)
+sim.reset(None, obs)
+sim.sync()
+rng = np.random.RandomState(0)
+for _ in range(3):
+    act = torch.as_tensor(rng.uniform(-1, 1, (n, sim.dof_action)).astype(np.float32), device=dev)
+    torch.cuda.synchronize()
+    sim.step(act, obs, rew, done, info)
+    sim.sync()
+world = dict(pos=(1.6, -1.1, 1.3), lookat=(0.3, 0.0, 0.3), fovy=50)                      # the robot, the table and the parts
+wrist = dict(pos=(0.0, 0.05, -0.05), quat=(0.0, 1.0, 0.0, 0.0), fovy=80, body="right_hand")  # along the gripper
+
+
+def median_ms(fn):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    with torch.cuda.stream(sim.torch_stream):
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms))
+
+
+cases = [("world64", 1, 64, True, True), ("world_wrist64", 2, 64, True, True), ("world128", 1, 128, True, True),
+         ("world64_flow_only", 1, 64, True, False), ("world64_velocity_only", 1, 64, False, True)]
+for name, ncam, size, flow, velocity in cases:
+    cams = [Camera(width=size, height=size, **c) for c in (world, wrist)[:ncam]]
+    sim.set_cameras(cams)
+    img = (torch.empty((n, ncam, size, size), device=dev), torch.empty((n, ncam, size, size), dtype=torch.int32, device=dev))
+    t_rays = median_ms(lambda: sim.render(out=img))
+    sim.set_flow(Flow(flow=flow, velocity=velocity))
+    out = sim.render_flow(images=True)
+    t_all = median_ms(lambda: sim.render_flow(images=True, out=out))
+    sim.set_normals(Normals(normal=True, shaded=False))
+    nout = sim.render_normals(images=True)
+    t_nrm = median_ms(lambda: sim.render_normals(images=True, out=nout))
+    torch.cuda.synchronize()
+    pixels = n * ncam * size * size
+    bytes_ = pixels * (8 + (12 if flow else 0) + (12 if velocity else 0))
+    bound_ms = bytes_ / HBM_BYTES_PER_S * 1e3
+    nrm_bound_ms = pixels * 20 / HBM_BYTES_PER_S * 1e3
+    row = dict(case=name, envs=n, cameras=ncam, width=size, height=size, flow=flow, velocity=velocity, reps=reps,
+               ms_rays=round(t_rays, 4), ms_flow=round(t_all - t_rays, 4), ms_total=round(t_all, 4),
+               hit_fraction=round(float((out["camera_segmentation"] >= 0).double().mean()), 3), bytes_bound_mb=round(bytes_ / 1e6, 1),
+               bytes_bound_ms=round(bound_ms, 4), ms_normals=round(t_nrm - t_rays, 4), normals_bytes_bound_ms=round(nrm_bound_ms, 4))
+    row["flow_over_bound"] = round(row["ms_flow"] / bound_ms, 2)
+    row["normals_over_bound"] = round(row["ms_normals"] / nrm_bound_ms, 2)
+    print(json.dumps(row), flush=True)
+sim.close()
