@@ -293,6 +293,72 @@ static void cam_free(fsim *s) {
   s->cam = nullptr;
 }
 
+// What fsim_set_cameras and fsim_set_rays (fsim_rays.hpp) read of the model blob to place a body-mounted frame and to build the static
+// geom rows
+struct CamMountTables {
+  std::vector<int> body_red, cg_type, cg_orig, cursor_body;
+  std::vector<float> relpos, relquat, cg_size, cg_rbound;
+};
+
+static int cam_mount_tables(const fsim *s, CamMountTables &t) {
+  if (!blob_i(s->blob, "body_red", t.body_red) || !blob_f(s->blob, "body_relpos", t.relpos) || !blob_f(s->blob, "body_relquat", t.relquat) ||
+      !blob_i(s->blob, "cg_type", t.cg_type) || !blob_i(s->blob, "cg_orig", t.cg_orig) || !blob_f(s->blob, "cg_size", t.cg_size) ||
+      !blob_f(s->blob, "cg_rbound", t.cg_rbound))
+    return FSIM_EINVAL;
+  if (s->m.agent == 2 && !blob_i(s->blob, "cursor_bodyid", t.cursor_body)) return FSIM_EINVAL;
+  return FSIM_OK;
+}
+
+// One d_cams row (CCW_*) of a frame (pos, quat wxyz) given in the frame of model body `body` (-1: the world), composed in double.
+// Nonzero: a pose that is not finite or has no orientation.
+static int cam_mount_row(const CamMountTables &t, int body, const float *pos, const float *quat, float *r) {
+  double q[4] = {quat[0], quat[1], quat[2], quat[3]}, p[3] = {pos[0], pos[1], pos[2]};
+  const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  if (!(qn > 1e-12) || !std::isfinite(qn) || !std::isfinite(p[0] + p[1] + p[2])) return 1;
+  for (double &x : q) x /= qn;
+  int rbody = 0, cur = -1;
+  if (body >= 0) { // (body_relpos, body_relquat) of the body in its reduced body (x) the frame's pose, in double
+    const int b = body;
+    const double rp[3] = {t.relpos[3 * b], t.relpos[3 * b + 1], t.relpos[3 * b + 2]}, rq[4] = {t.relquat[4 * b], t.relquat[4 * b + 1], t.relquat[4 * b + 2], t.relquat[4 * b + 3]};
+    const double u[3] = {rq[1], rq[2], rq[3]};
+    const double tt[3] = {2 * (u[1] * p[2] - u[2] * p[1]), 2 * (u[2] * p[0] - u[0] * p[2]), 2 * (u[0] * p[1] - u[1] * p[0])};
+    const double np_[3] = {rp[0] + p[0] + rq[0] * tt[0] + (u[1] * tt[2] - u[2] * tt[1]), rp[1] + p[1] + rq[0] * tt[1] + (u[2] * tt[0] - u[0] * tt[2]),
+                           rp[2] + p[2] + rq[0] * tt[2] + (u[0] * tt[1] - u[1] * tt[0])};
+    const double nq[4] = {rq[0] * q[0] - rq[1] * q[1] - rq[2] * q[2] - rq[3] * q[3], rq[0] * q[1] + rq[1] * q[0] + rq[2] * q[3] - rq[3] * q[2],
+                          rq[0] * q[2] - rq[1] * q[3] + rq[2] * q[0] + rq[3] * q[1], rq[0] * q[3] + rq[1] * q[2] - rq[2] * q[1] + rq[3] * q[0]};
+    for (int j = 0; j < 3; j++) p[j] = np_[j];
+    for (int j = 0; j < 4; j++) q[j] = nq[j];
+    rbody = t.body_red[b];
+    for (size_t j = 0; j < t.cursor_body.size(); j++)
+      if (t.cursor_body[j] == b) cur = (int)j; // a cursor moves with the env's cursor position, not with its (world) body
+  }
+  r[CCW_RBODY] = cam_bits(rbody); r[CCW_CURSOR] = cam_bits(cur);
+  for (int j = 0; j < 3; j++) r[CCW_POS + j] = (float)p[j];
+  for (int j = 0; j < 4; j++) r[CCW_QUAT + j] = (float)q[j];
+  return 0;
+}
+
+// The static rows (CAM_SW words) of every colliding geom, with the hull-plane slices checked; who: the caller's name for the messages
+static int cam_geom_rows(const DModel &m, const CamMountTables &t, const char *who, int n_planes, const float *hull_planes, const int32_t *hull_adr,
+                         const int32_t *hull_num, std::vector<float> &cg) {
+  cg.assign((size_t)CAM_SW * m.ncg, 0.0f);
+  for (int g = 0; g < m.ncg; g++) {
+    float *r = cg.data() + CAM_SW * g;
+    for (int j = 0; j < 3; j++) r[j] = t.cg_size[3 * g + j];
+    r[3] = t.cg_rbound[g];
+    int adr = 0, num = 0;
+    if (t.cg_type[g] == GT_MESH) {
+      if (!hull_adr || !hull_num || !hull_planes) FAIL(FSIM_EINVAL, "%s: colliding geom %d is a convex mesh and no hull planes were given", who, g);
+      adr = hull_adr[g]; num = hull_num[g];
+      if (num < 4 || adr < 0 || adr + num > n_planes) FAIL(FSIM_EINVAL, "%s: hull planes of colliding geom %d out of range (%d + %d of %d)", who, g, adr, num, n_planes);
+    }
+    r[4] = cam_bits(t.cg_type[g]); r[5] = cam_bits(adr); r[6] = cam_bits(num); r[7] = cam_bits(t.cg_orig[g]);
+  }
+  for (int i = 0; i < 4 * n_planes; i++)
+    if (!std::isfinite(hull_planes[i])) FAIL(FSIM_EINVAL, "%s: hull plane table holds a non-finite value", who);
+  return FSIM_OK;
+}
+
 extern "C" int fsim_set_cameras(fsim_t *s, int n_cam, const fsim_camera_t *cams, int n_planes, const float *hull_planes, const int32_t *hull_adr,
                                 const int32_t *hull_num) {
   if (!s || !cams) FAIL(FSIM_EINVAL, "fsim_set_cameras: null argument");
@@ -300,13 +366,8 @@ extern "C" int fsim_set_cameras(fsim_t *s, int n_cam, const fsim_camera_t *cams,
   const DModel &m = s->m;
   if (m.ncg > FSIM_CAM_MAX_GEOMS) FAIL(FSIM_EINVAL, "fsim_set_cameras: %d colliding geoms (the ray pass stages at most %d)", m.ncg, FSIM_CAM_MAX_GEOMS);
   if (n_planes < 0 || n_planes > FSIM_CAM_MAX_PLANES) FAIL(FSIM_EINVAL, "fsim_set_cameras: %d hull planes (at most %d)", n_planes, FSIM_CAM_MAX_PLANES);
-  std::vector<int> body_red, cg_type, cg_orig, cursor_body;
-  std::vector<float> relpos, relquat, cg_size, cg_rbound;
-  if (!blob_i(s->blob, "body_red", body_red) || !blob_f(s->blob, "body_relpos", relpos) || !blob_f(s->blob, "body_relquat", relquat) ||
-      !blob_i(s->blob, "cg_type", cg_type) || !blob_i(s->blob, "cg_orig", cg_orig) || !blob_f(s->blob, "cg_size", cg_size) ||
-      !blob_f(s->blob, "cg_rbound", cg_rbound))
-    return FSIM_EINVAL;
-  if (m.agent == 2 && !blob_i(s->blob, "cursor_bodyid", cursor_body)) return FSIM_EINVAL;
+  CamMountTables mt;
+  { int rc_ = cam_mount_tables(s, mt); if (rc_) return rc_; }
   CamState c;
   c.ncam = n_cam; c.W = cams[0].width; c.H = cams[0].height; c.nplanes = n_planes;
   std::vector<float> crow((size_t)CCW_WORDS * n_cam, 0.0f);
@@ -318,48 +379,12 @@ extern "C" int fsim_set_cameras(fsim_t *s, int n_cam, const fsim_camera_t *cams,
     if (k.width < 1 || k.height < 1 || k.width > FSIM_CAM_MAX_SIZE || k.height > FSIM_CAM_MAX_SIZE)
       FAIL(FSIM_EINVAL, "camera %d: size %d x %d (1 .. %d each)", i, k.width, k.height, FSIM_CAM_MAX_SIZE);
     if (k.width != c.W || k.height != c.H) FAIL(FSIM_EINVAL, "camera %d: size %d x %d differs from camera 0's %d x %d", i, k.width, k.height, c.W, c.H);
-    double q[4] = {k.quat[0], k.quat[1], k.quat[2], k.quat[3]}, p[3] = {k.pos[0], k.pos[1], k.pos[2]};
-    const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (!(qn > 1e-12) || !std::isfinite(qn) || !std::isfinite(p[0] + p[1] + p[2])) FAIL(FSIM_EINVAL, "camera %d: bad pose", i);
-    for (double &x : q) x /= qn;
-    int rbody = 0, cur = -1;
-    if (k.body >= 0) { // (body_relpos, body_relquat) of the body in its reduced body (x) the camera pose, in double
-      const int b = k.body;
-      const double rp[3] = {relpos[3 * b], relpos[3 * b + 1], relpos[3 * b + 2]}, rq[4] = {relquat[4 * b], relquat[4 * b + 1], relquat[4 * b + 2], relquat[4 * b + 3]};
-      const double u[3] = {rq[1], rq[2], rq[3]};
-      const double t[3] = {2 * (u[1] * p[2] - u[2] * p[1]), 2 * (u[2] * p[0] - u[0] * p[2]), 2 * (u[0] * p[1] - u[1] * p[0])};
-      const double np_[3] = {rp[0] + p[0] + rq[0] * t[0] + (u[1] * t[2] - u[2] * t[1]), rp[1] + p[1] + rq[0] * t[1] + (u[2] * t[0] - u[0] * t[2]),
-                             rp[2] + p[2] + rq[0] * t[2] + (u[0] * t[1] - u[1] * t[0])};
-      const double nq[4] = {rq[0] * q[0] - rq[1] * q[1] - rq[2] * q[2] - rq[3] * q[3], rq[0] * q[1] + rq[1] * q[0] + rq[2] * q[3] - rq[3] * q[2],
-                            rq[0] * q[2] - rq[1] * q[3] + rq[2] * q[0] + rq[3] * q[1], rq[0] * q[3] + rq[1] * q[2] - rq[2] * q[1] + rq[3] * q[0]};
-      for (int j = 0; j < 3; j++) p[j] = np_[j];
-      for (int j = 0; j < 4; j++) q[j] = nq[j];
-      rbody = body_red[b];
-      for (size_t j = 0; j < cursor_body.size(); j++)
-        if (cursor_body[j] == b) cur = (int)j; // a cursor moves with the env's cursor position, not with its (world) body
-    }
-    float *r = crow.data() + CCW_WORDS * i;
-    r[CCW_RBODY] = cam_bits(rbody); r[CCW_CURSOR] = cam_bits(cur);
-    for (int j = 0; j < 3; j++) r[CCW_POS + j] = (float)p[j];
-    for (int j = 0; j < 4; j++) r[CCW_QUAT + j] = (float)q[j];
+    if (cam_mount_row(mt, k.body, k.pos, k.quat, crow.data() + CCW_WORDS * i)) FAIL(FSIM_EINVAL, "camera %d: bad pose", i);
     c.slope[i] = (float)(tan(k.fovy_deg * (3.14159265358979323846 / 360.0)) / (0.5 * c.H));
     c.znear[i] = k.znear; c.zfar[i] = k.zfar;
   }
-  std::vector<float> cg((size_t)CAM_SW * m.ncg, 0.0f);
-  for (int g = 0; g < m.ncg; g++) {
-    float *r = cg.data() + CAM_SW * g;
-    for (int j = 0; j < 3; j++) r[j] = cg_size[3 * g + j];
-    r[3] = cg_rbound[g];
-    int adr = 0, num = 0;
-    if (cg_type[g] == GT_MESH) {
-      if (!hull_adr || !hull_num || !hull_planes) FAIL(FSIM_EINVAL, "fsim_set_cameras: colliding geom %d is a convex mesh and no hull planes were given", g);
-      adr = hull_adr[g]; num = hull_num[g];
-      if (num < 4 || adr < 0 || adr + num > n_planes) FAIL(FSIM_EINVAL, "fsim_set_cameras: hull planes of colliding geom %d out of range (%d + %d of %d)", g, adr, num, n_planes);
-    }
-    r[4] = cam_bits(cg_type[g]); r[5] = cam_bits(adr); r[6] = cam_bits(num); r[7] = cam_bits(cg_orig[g]);
-  }
-  for (int i = 0; i < 4 * n_planes; i++)
-    if (!std::isfinite(hull_planes[i])) FAIL(FSIM_EINVAL, "fsim_set_cameras: hull plane table holds a non-finite value");
+  std::vector<float> cg;
+  { int rc_ = cam_geom_rows(m, mt, "fsim_set_cameras", n_planes, hull_planes, hull_adr, hull_num, cg); if (rc_) return rc_; }
   c.pstride = (CAM_PW * (m.ncg + n_cam) + 3) / 4 * 4;
   HIPCHK(hipSetDevice(s->device));
   { int rc_ = settle(s); if (rc_) return rc_; }

@@ -360,9 +360,10 @@ class FurnitureBatchEnv:
     voxels = None
     normals = None
     flow = None
+    rays = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -387,7 +388,11 @@ class FurnitureBatchEnv:
         m/s) and / or camera_velocity (float32 [n, C, H, W, 3]: that point's world-frame velocity in m/s), (0, 0, 0) where a pixel sees
         nothing, from one fsim_render_flow call after the others (one more ray pass of the same state when there are any).  With
         point_cloud as well and velocity=True, the observations also hold point_cloud_velocity (camera_velocity gathered as
-        point_cloud_normal is)."""
+        point_cloud_normal is).
+        rays: a furniture_amd.rays.RaySet (needs no cameras) -- the observations then also hold ray_distance (float32 [n, R], metres
+        along each ray of the set's sensors, -1 where nothing is hit), ray_geom (int32 [n, R], model geom id as in camera_segmentation,
+        -1 = nothing) and, with normal=True, ray_normal (float32 [n, R, 3], the world-frame outward unit normal at the hit point,
+        (0, 0, 0) = nothing), from one fsim_cast_rays call."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -400,6 +405,9 @@ class FurnitureBatchEnv:
         if flow is not None:
             from .flow import check as check_flow
             check_flow(flow, list(cameras) if cameras else None)
+        if rays is not None:
+            from .rays import check as check_rays
+            check_rays(rays)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -516,6 +524,10 @@ class FurnitureBatchEnv:
                 for k, (sh, dt) in shapes().items():
                     out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
                 setattr(self, bufs, out)
+        self.rays = rays
+        if rays is not None:  # (without rays: no allocation, no launch, the same observation dict)
+            self.sim.set_rays(rays)
+            self._ray_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.ray_shapes().items()}
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -561,6 +573,12 @@ class FurnitureBatchEnv:
                 sp.append(("camera_velocity", spaces.Box(-np.inf, np.inf, shape=shape + (3,), dtype=np.float32)))
             if self.flow.velocity and self.point_cloud is not None:
                 sp.append(("point_cloud_velocity", spaces.Box(-np.inf, np.inf, shape=per + (3,), dtype=np.float32)))
+        if self.rays is not None:
+            r = self.rays.n_rays
+            sp.append(("ray_distance", spaces.Box(-1.0, np.inf, shape=(r,), dtype=np.float32)))
+            sp.append(("ray_geom", spaces.Box(-1, self.model.ngeom - 1, shape=(r,), dtype=np.int32)))
+            if self.rays.normal:
+                sp.append(("ray_normal", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -574,7 +592,8 @@ class FurnitureBatchEnv:
         the point cloud when one is set (images and points from one fsim_render_points call: one ray pass) and the voxel grid when one is
         set (from one fsim_render_voxels call; with a point cloud as well, that is a second ray pass of the same state) and the normal /
         shaded images when they are set (from one fsim_render_normals call, after the others: one more ray pass when there are any) and
-        the flow / velocity images when they are set (from one fsim_render_flow call, last: again one more ray pass when there are any)"""
+        the flow / velocity images when they are set (from one fsim_render_flow call, last: again one more ray pass when there are any) and
+        the ray sensors' outputs when a ray set is given (from one fsim_cast_rays call)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -600,6 +619,8 @@ class FurnitureBatchEnv:
                 out["point_cloud_velocity"] = self._at_points(res["camera_velocity"])
         if self.cameras and self.point_cloud is None and self.voxels is None and self.normals is None and self.flow is None:
             out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
+        if self.rays is not None:  # one fsim_cast_rays call; independent of the cameras
+            out.update(self.sim.cast_rays(out=self._ray_out))
         return out
 
     def _at_points(self, image):
@@ -944,7 +965,7 @@ class _SingleEnv:
             dev = old.sim.device.index or 0
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
-                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow)
+                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

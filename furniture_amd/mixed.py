@@ -53,6 +53,9 @@ class FurnitureMixedBatchEnv:
         if kw.pop("flow", None) is not None:
             raise NotImplementedError("flow= is not supported by the mixed-furniture batch (one camera set per FurnitureBatchEnv): "
                                       "make one FurnitureBatchEnv per furniture instead")
+        if kw.pop("rays", None) is not None:
+            raise NotImplementedError("rays= is not supported by the mixed-furniture batch (one ray set per FurnitureBatchEnv): "
+                                      "make one FurnitureBatchEnv per furniture instead")
         cfg = config if config is not None else make_config()
         for key, v in kw.items():
             setattr(cfg, key, v)

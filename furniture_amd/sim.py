@@ -55,6 +55,12 @@ class StatePtrs(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in _names]
 
 
+class FsimRaySensor(ctypes.Structure):
+    """fsim_ray_sensor_t (include/fsim_rays.h)"""
+    _fields_ = [("body", ctypes.c_int32), ("pos", ctypes.c_float * 3), ("quat", ctypes.c_float * 4), ("tmin", ctypes.c_float), ("tmax", ctypes.c_float),
+                ("first_ray", ctypes.c_int32), ("n_rays", ctypes.c_int32), ("exclude", ctypes.c_uint32 * 3)]
+
+
 def library_path():
     return _LIBPATH
 
@@ -62,7 +68,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -168,6 +174,8 @@ def lib():
         L.fsim_set_normals.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float]
         L.fsim_render_normals.argtypes = [ctypes.c_void_p] * 5
         L.fsim_render_flow.argtypes = [ctypes.c_void_p] * 5
+        L.fsim_set_rays.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fsim_cast_rays.argtypes = [ctypes.c_void_p] * 4
         _LIB = L
     return _LIB
 
@@ -191,6 +199,8 @@ VOXELS_SYMBOLS = ["fsim_set_voxels", "fsim_render_voxels"]
 NORMALS_SYMBOLS = ["fsim_set_normals", "fsim_render_normals"]
 # the flow / velocity image entry point: a header of its own (include/fsim_flow.h), exported by the same library
 FLOW_SYMBOLS = ["fsim_render_flow"]
+# the ray-sensor entry points: a header of their own (include/fsim_rays.h), exported by the same library
+RAY_SYMBOLS = ["fsim_set_rays", "fsim_cast_rays"]
 
 
 def preassembled_rows(model, preassembled):
@@ -646,6 +656,68 @@ class FSim:
         if not self.cameras:
             raise FsimError("render_flow: no cameras set (FSim.set_cameras)")
         return self._render_derived("render_flow", lib().fsim_render_flow, ("camera_flow", "camera_velocity"), self.flow_shapes(), images, out)
+
+    # -- ray-cast range sensors and lidar (include/fsim_rays.h, furniture_amd/rays.py) ---------------------------------------------------
+    rays = None
+
+    def set_rays(self, ray_set):
+        """Replace the handle's ray set (a furniture_amd.rays.RaySet; None clears it); checked on the host first, then by the library.
+        Independent of the cameras: neither needs nor disturbs the other."""
+        from .camera import hull_plane_table
+        from .rays import RaySet, sensor_table
+        if ray_set is None:
+            self._chk(lib().fsim_set_rays(self._h, 0, None, 0, None, 0, None, None, None))
+            self.rays = None
+            return
+        if not isinstance(ray_set, RaySet):
+            raise TypeError("set_rays: a furniture_amd.rays.RaySet, not %r" % type(ray_set).__name__)
+        tab, dirs = sensor_table(self.cm, ray_set)
+        planes, adr, num = hull_plane_table(self.cm)
+        self._chk(lib().fsim_set_rays(self._h, len(tab), ctypes.addressof(tab), len(dirs), dirs.ctypes.data, len(planes),
+                                      planes.ctypes.data if len(planes) else None, adr.ctypes.data, num.ctypes.data))
+        self.rays = ray_set
+
+    def ray_shapes(self):
+        """{key: (shape, dtype)} of cast_rays' outputs (without the n_envs dimension)"""
+        torch = self.torch
+        if self.rays is None:
+            raise FsimError("ray_shapes: no rays set (FSim.set_rays)")
+        r = self.rays.n_rays
+        out = {"ray_distance": ((r,), torch.float32), "ray_geom": ((r,), torch.int32)}
+        if self.rays.normal:
+            out["ray_normal"] = ((r, 3), torch.float32)
+        return out
+
+    def sensor_slices(self):
+        """{sensor index: slice of the ray dimension of cast_rays' outputs}"""
+        if self.rays is None:
+            raise FsimError("sensor_slices: no rays set (FSim.set_rays)")
+        return self.rays.sensor_slices()
+
+    def cast_rays(self, out=None):
+        """Cast every ray of the ray set in every env (include/fsim_rays.h), for the state sync() leaves -> dict of device tensors:
+        ray_distance (float32 [n, R], metres along the ray, -1 = nothing hit), ray_geom (int32 [n, R], model geom id as in
+        camera_segmentation, -1 = nothing hit) and, when the ray set asks for it, ray_normal (float32 [n, R, 3], the world-frame outward
+        unit normal at the hit point, (0, 0, 0) = nothing hit).  out: a dict of such tensors to write into instead of new ones; a key
+        that is there alone is cast alone.  Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if self.rays is None:
+            raise FsimError("cast_rays: no rays set (FSim.set_rays)")
+        want = self.ray_shapes()
+        if out is not None:
+            if not out or any(k not in want for k in out):
+                raise ValueError("cast_rays: out holds %s (of %s)" % (sorted(out), sorted(want)))
+            want = {k: want[k] for k in want if k in out}
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "cast_rays: out[%r] of the wrong shape / type" % k
+            res[k] = t
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_cast_rays(self._h, *[res[k].data_ptr() if k in res else None for k in ("ray_distance", "ray_geom", "ray_normal")]))
+        cur.wait_stream(self.torch_stream)
+        return res
 
     def kernel_time_ms(self):
         ms, n = ctypes.c_double(), ctypes.c_int32()
