@@ -511,6 +511,7 @@ struct VoxState; // fsim_voxels.hpp
 struct NrmState; // fsim_normals.hpp
 struct FlwState; // fsim_flow.hpp
 struct RayState; // fsim_rays.hpp
+struct ProbeState; // fsim_probes.hpp
 struct KernelSet { const char *name; PhysicsFn physics; EnvStepFn env_step; PhysicsFn physics_mw; EnvStepFn env_step_mw; EnvStepXFn env_step_x; };
 enum { MW_OFF = 0, MW_RULE = 1, MW_ALL = 2 }; // fsim::mw_mode
 
@@ -594,6 +595,7 @@ struct fsim {
   NrmState *nrm = nullptr; // normal / shaded image settings and scratch (fsim_set_normals): nothing is allocated or launched without them
   FlwState *flw = nullptr; // flow / velocity image scratch (the first fsim_render_flow): nothing is allocated or launched without that call
   RayState *ray = nullptr; // ray sensors: tables and pose scratch (fsim_set_rays): nothing is allocated or launched without them
+  ProbeState *probe = nullptr; // distance probes: tables and pose scratch (fsim_set_probes): nothing is allocated or launched without them
 };
 
 static void la_policy(fsim *s);
@@ -1010,6 +1012,7 @@ static void vox_free(fsim *s);
 static void nrm_free(fsim *s);
 static void flw_free(fsim *s);
 static void ray_free(fsim *s);
+static void probe_free(fsim *s);
 extern "C" void fsim_destroy(fsim_t *s) {
   if (!s) return;
   hipSetDevice(s->device);
@@ -1020,6 +1023,7 @@ extern "C" void fsim_destroy(fsim_t *s) {
   nrm_free(s);
   flw_free(s);
   ray_free(s);
+  probe_free(s);
   hipFree(s->d_sh_state); hipFree(s->d_sh_obs); hipFree(s->d_sh_prog); hipFree(s->d_sh_serial); hipFree(s->d_tab_serial); hipFree(s->d_sh_jobs);
   if (s->xfer) { hipStreamSynchronize(s->xfer); hipStreamDestroy(s->xfer); }
   hipFree(s->d_ly_r[0]); hipFree(s->d_ly_r[1]); hipFree(s->d_ly_r[2]); hipFree(s->d_prev); hipFree(s->d_ovf_list); hipFree(s->d_ovf_list2);
@@ -1674,3 +1678,4 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
 #include "fsim_normals.hpp"
 #include "fsim_flow.hpp"
 #include "fsim_rays.hpp"
+#include "fsim_probes.hpp"

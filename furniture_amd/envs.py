@@ -361,9 +361,10 @@ class FurnitureBatchEnv:
     normals = None
     flow = None
     rays = None
+    probes = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -392,7 +393,12 @@ class FurnitureBatchEnv:
         rays: a furniture_amd.rays.RaySet (needs no cameras) -- the observations then also hold ray_distance (float32 [n, R], metres
         along each ray of the set's sensors, -1 where nothing is hit), ray_geom (int32 [n, R], model geom id as in camera_segmentation,
         -1 = nothing) and, with normal=True, ray_normal (float32 [n, R, 3], the world-frame outward unit normal at the hit point,
-        (0, 0, 0) = nothing), from one fsim_cast_rays call."""
+        (0, 0, 0) = nothing), from one fsim_cast_rays call.
+        probes: a furniture_amd.probes.ProbeSet (needs no cameras or rays) -- the observations then also hold probe_distance (float32
+        [n, P], metres from each probe point of the set's sensors to the nearest surface, negative inside a solid, the sensor's dmax where
+        nothing is within it), probe_geom (int32 [n, P], model geom id as in camera_segmentation, -1 = nothing) and, with gradient=True,
+        probe_gradient (float32 [n, P, 3], the world-frame unit gradient of the distance, (0, 0, 0) = nothing), from one
+        fsim_probe_distance call."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -408,6 +414,9 @@ class FurnitureBatchEnv:
         if rays is not None:
             from .rays import check as check_rays
             check_rays(rays)
+        if probes is not None:
+            from .probes import check as check_probes
+            check_probes(probes)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -528,6 +537,10 @@ class FurnitureBatchEnv:
         if rays is not None:  # (without rays: no allocation, no launch, the same observation dict)
             self.sim.set_rays(rays)
             self._ray_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.ray_shapes().items()}
+        self.probes = probes
+        if probes is not None:  # (without probes: no allocation, no launch, the same observation dict)
+            self.sim.set_probes(probes)
+            self._probe_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.probe_shapes().items()}
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -579,6 +592,12 @@ class FurnitureBatchEnv:
             sp.append(("ray_geom", spaces.Box(-1, self.model.ngeom - 1, shape=(r,), dtype=np.int32)))
             if self.rays.normal:
                 sp.append(("ray_normal", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
+        if self.probes is not None:
+            r = self.probes.n_probes
+            sp.append(("probe_distance", spaces.Box(-np.inf, max(k.dmax for k in self.probes.sensors), shape=(r,), dtype=np.float32)))
+            sp.append(("probe_geom", spaces.Box(-1, self.model.ngeom - 1, shape=(r,), dtype=np.int32)))
+            if self.probes.gradient:
+                sp.append(("probe_gradient", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -593,7 +612,8 @@ class FurnitureBatchEnv:
         set (from one fsim_render_voxels call; with a point cloud as well, that is a second ray pass of the same state) and the normal /
         shaded images when they are set (from one fsim_render_normals call, after the others: one more ray pass when there are any) and
         the flow / velocity images when they are set (from one fsim_render_flow call, last: again one more ray pass when there are any) and
-        the ray sensors' outputs when a ray set is given (from one fsim_cast_rays call)"""
+        the ray sensors' outputs when a ray set is given (from one fsim_cast_rays call) and the distance probes' outputs when a probe set
+        is given (from one fsim_probe_distance call)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -621,6 +641,8 @@ class FurnitureBatchEnv:
             out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
         if self.rays is not None:  # one fsim_cast_rays call; independent of the cameras
             out.update(self.sim.cast_rays(out=self._ray_out))
+        if self.probes is not None:  # one fsim_probe_distance call; independent of the cameras and the rays
+            out.update(self.sim.probe_distance(out=self._probe_out))
         return out
 
     def _at_points(self, image):
@@ -965,7 +987,8 @@ class _SingleEnv:
             dev = old.sim.device.index or 0
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
-                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays)
+                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays,
+                                         probes=old.probes)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

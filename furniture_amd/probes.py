@@ -1,0 +1,146 @@
+"""Signed-distance proximity probes computed on the device (include/fsim_probes.h, csrc/fsim_probes.hpp).
+
+A ProbeSensor is a frame fixed in the world or mounted on a model body with a set of probe points in that frame, a largest distance dmax
+in metres and a set of geoms it does not see.  Per probe the device gives probe_distance (float32 metres to the nearest surface in any
+direction, negative inside a solid: the penetration depth; dmax where nothing is within dmax: MuJoCo's distmax convention), probe_geom
+(int32 model geom id of that surface, the numbering of camera_segmentation and ray_geom, so furniture_amd.camera.geom_labels applies;
+-1 = nothing) and, when asked for, probe_gradient (float32 world-frame unit gradient of the distance: the way to move to get away from the
+surface, (0, 0, 0) = nothing).  Where the distance is exact the nearest surface point is p - probe_distance * probe_gradient.  A convex
+hull's distance is the plane bound: exact inside the hull and wherever the nearest feature is a face, a lower bound near edges and
+vertices outside.  The probes see the collision geometry the cameras and rays see; they need neither.  The contract is the header's.
+"""
+
+import numpy as np
+
+from .camera import MAX_GEOMS
+from .rays import exclude_mask  # (the rule is shared; its message for an unknown geom id still says "RaySensor": to be made neutral in rays.py)
+
+MAX_SENSORS = 16   # FSIM_PROBE_MAX_SENSORS
+MAX_PROBES = 4096  # FSIM_PROBE_MAX_PROBES, per env over all sensors
+
+
+class ProbeSensor:
+    """One sensor: fixed in the world (body=None) or mounted on the model body named ``body``; pos / quat (wxyz) in that frame.
+    points: [k, 3] in the sensor frame, metres.  dmax: the largest distance reported, 0 < dmax < inf.  exclude: "body" (the default: a
+    mounted sensor does not see the geoms that move rigidly with its mount; furniture_amd.rays.exclude_mask), None (sees everything) or
+    a list of model geom ids."""
+
+    def __init__(self, pos, points, quat=None, body=None, dmax=1.0, exclude="body"):
+        self.pos = np.asarray(pos, dtype=np.float64).reshape(3)
+        q = np.asarray((1.0, 0.0, 0.0, 0.0) if quat is None else quat, dtype=np.float64).reshape(4)
+        if not np.all(np.isfinite(self.pos)) or not np.all(np.isfinite(q)) or np.linalg.norm(q) < 1e-12:
+            raise ValueError("ProbeSensor: bad pose")
+        self.quat = q / np.linalg.norm(q)
+        p = np.asarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3 or len(p) < 1:
+            raise ValueError("ProbeSensor: points is a [k, 3] array with k >= 1 (got shape %s)" % (p.shape,))
+        if not np.all(np.isfinite(p)):
+            raise ValueError("ProbeSensor: a point is not finite")
+        self.points = p.copy()
+        self.dmax = float(dmax)
+        if not (self.dmax > 0.0 and np.isfinite(self.dmax)):
+            raise ValueError("ProbeSensor: needs 0 < dmax < inf (got %g)" % self.dmax)
+        if not (exclude is None or exclude == "body" or (not isinstance(exclude, str) and all(int(g) == g for g in exclude))):
+            raise ValueError("ProbeSensor: exclude is \"body\", None or a list of model geom ids (got %r)" % (exclude,))
+        self.exclude = exclude if exclude is None or isinstance(exclude, str) else [int(g) for g in exclude]
+        self.body = body
+
+    @property
+    def n_probes(self):
+        return len(self.points)
+
+    def body_id(self, model):
+        if self.body is None:
+            return -1
+        names = model.meta["body_names"]
+        if self.body not in names:
+            raise ValueError("ProbeSensor: unknown body %r (model %s + %s)" % (self.body, model.meta.get("agent"), model.meta.get("furniture_name")))
+        return names.index(self.body)
+
+    def world_pose(self, body_xpos=None, body_xquat=None):
+        """(origin, 3 x 3 sensor -> world rotation) given the world pose of the sensor's body (ignored for a world sensor)."""
+        from .camera import quat_to_mat
+        if self.body is None:
+            return self.pos.copy(), quat_to_mat(self.quat)
+        R = quat_to_mat(body_xquat)
+        return np.asarray(body_xpos, dtype=np.float64) + R @ self.pos, R @ quat_to_mat(self.quat)
+
+    def __repr__(self):
+        return "ProbeSensor(pos=%s, %d probes, body=%r, dmax %g, exclude=%r)" % (self.pos.tolist(), self.n_probes, self.body, self.dmax, self.exclude)
+
+
+def grid_points(lo, hi, shape):
+    """[nx * ny * nz, 3] cell centres of the box lo .. hi cut into shape = (nx, ny, nz) cells: x outer, z inner, so the outputs of the
+    sensor reshape to (nx, ny, nz)."""
+    lo, hi = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    if len(tuple(shape)) != 3 or any(int(k) != k or k < 1 for k in shape):
+        raise ValueError("grid_points: shape is three positive integers (got %r)" % (shape,))
+    if not np.all(np.isfinite(lo)) or not np.all(np.isfinite(hi)) or not np.all(hi > lo):
+        raise ValueError("grid_points: needs finite lo < hi per axis (got %s, %s)" % (lo.tolist(), hi.tolist()))
+    ax = [lo[a] + (np.arange(int(shape[a])) + 0.5) * (hi[a] - lo[a]) / int(shape[a]) for a in range(3)]
+    return np.stack(np.meshgrid(*ax, indexing="ij"), axis=-1).reshape(-1, 3)
+
+
+class ProbeSet:
+    """The probe sensors of a handle or env, in the style of RaySet.  gradient: add probe_gradient to the outputs."""
+
+    def __init__(self, sensors, gradient=False):
+        self.sensors = [sensors] if isinstance(sensors, ProbeSensor) else list(sensors)
+        if not isinstance(gradient, (bool, np.bool_)):
+            raise ValueError("ProbeSet: gradient is a boolean (got %r)" % (gradient,))
+        self.gradient = bool(gradient)
+        self.check()
+
+    def check(self):
+        """Host-side check of the probe set, before any device work."""
+        for k in self.sensors:
+            if not isinstance(k, ProbeSensor):
+                raise TypeError("ProbeSet: a list of furniture_amd.probes.ProbeSensor, not %r" % type(k).__name__)
+        if not 1 <= len(self.sensors) <= MAX_SENSORS:
+            raise ValueError("ProbeSet: %d sensors (1 .. %d)" % (len(self.sensors), MAX_SENSORS))
+        if self.n_probes > MAX_PROBES:
+            raise ValueError("ProbeSet: %d probes over all sensors (at most %d)" % (self.n_probes, MAX_PROBES))
+
+    @property
+    def n_probes(self):
+        return sum(k.n_probes for k in self.sensors)
+
+    def sensor_slices(self):
+        """{sensor index: slice of the probe dimension of the outputs}"""
+        out, at = {}, 0
+        for i, k in enumerate(self.sensors):
+            out[i] = slice(at, at + k.n_probes)
+            at += k.n_probes
+        return out
+
+    def __repr__(self):
+        return "ProbeSet(%d sensors, %d probes, gradient=%r)" % (len(self.sensors), self.n_probes, self.gradient)
+
+
+def check(spec):
+    """Host-side check of a probes= argument, before any device work."""
+    if not isinstance(spec, ProbeSet):
+        raise TypeError("probes: a furniture_amd.probes.ProbeSet, not %r" % type(spec).__name__)
+    spec.check()
+
+
+def sensor_table(model, probe_set):
+    """(fsim_probe_sensor_t array, float32 [P, 3] points) of a probe set against a compiled model (checked here first, then again by
+    the library)."""
+    from .sim import FsimProbeSensor
+    check(probe_set)
+    ncg = len(model.arrays["cg_orig"])
+    if ncg > MAX_GEOMS:
+        raise ValueError("probes: the model has %d colliding geoms (at most %d)" % (ncg, MAX_GEOMS))
+    tab = (FsimProbeSensor * len(probe_set.sensors))()
+    at = 0
+    for i, k in enumerate(probe_set.sensors):
+        bits = np.zeros(3, dtype=np.uint32)
+        for g in np.nonzero(exclude_mask(model, k))[0]:
+            bits[g >> 5] |= np.uint32(1) << np.uint32(g & 31)
+        t = tab[i]
+        t.body, t.dmax, t.first_probe, t.n_probes = k.body_id(model), k.dmax, at, k.n_probes
+        t.pos[:], t.quat[:], t.exclude[:] = k.pos.tolist(), k.quat.tolist(), [int(b) for b in bits]
+        at += k.n_probes
+    pts = np.ascontiguousarray(np.concatenate([k.points for k in probe_set.sensors]), dtype=np.float32)
+    return tab, pts

@@ -61,6 +61,12 @@ class FsimRaySensor(ctypes.Structure):
                 ("first_ray", ctypes.c_int32), ("n_rays", ctypes.c_int32), ("exclude", ctypes.c_uint32 * 3)]
 
 
+class FsimProbeSensor(ctypes.Structure):
+    """fsim_probe_sensor_t (include/fsim_probes.h)"""
+    _fields_ = [("body", ctypes.c_int32), ("pos", ctypes.c_float * 3), ("quat", ctypes.c_float * 4), ("dmax", ctypes.c_float),
+                ("first_probe", ctypes.c_int32), ("n_probes", ctypes.c_int32), ("exclude", ctypes.c_uint32 * 3)]
+
+
 def library_path():
     return _LIBPATH
 
@@ -68,7 +74,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -176,6 +182,8 @@ def lib():
         L.fsim_render_flow.argtypes = [ctypes.c_void_p] * 5
         L.fsim_set_rays.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fsim_cast_rays.argtypes = [ctypes.c_void_p] * 4
+        L.fsim_set_probes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fsim_probe_distance.argtypes = [ctypes.c_void_p] * 4
         _LIB = L
     return _LIB
 
@@ -201,6 +209,8 @@ NORMALS_SYMBOLS = ["fsim_set_normals", "fsim_render_normals"]
 FLOW_SYMBOLS = ["fsim_render_flow"]
 # the ray-sensor entry points: a header of their own (include/fsim_rays.h), exported by the same library
 RAY_SYMBOLS = ["fsim_set_rays", "fsim_cast_rays"]
+# the distance-probe entry points: a header of their own (include/fsim_probes.h), exported by the same library
+PROBE_SYMBOLS = ["fsim_set_probes", "fsim_probe_distance"]
 
 
 def preassembled_rows(model, preassembled):
@@ -716,6 +726,64 @@ class FSim:
         cur = torch.cuda.current_stream(self.device)
         self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
         self._chk(lib().fsim_cast_rays(self._h, *[res[k].data_ptr() if k in res else None for k in ("ray_distance", "ray_geom", "ray_normal")]))
+        cur.wait_stream(self.torch_stream)
+        return res
+
+    # -- signed-distance proximity probes (include/fsim_probes.h, furniture_amd/probes.py) ------------------------------------------------
+    probes = None
+
+    def set_probes(self, probe_set):
+        """Replace the handle's probe set (a furniture_amd.probes.ProbeSet; None clears it); checked on the host first, then by the
+        library.  Independent of the cameras and the rays: needs and disturbs neither."""
+        from .camera import hull_plane_table
+        from .probes import ProbeSet, sensor_table
+        if probe_set is None:
+            self._chk(lib().fsim_set_probes(self._h, 0, None, 0, None, 0, None, None, None))
+            self.probes = None
+            return
+        if not isinstance(probe_set, ProbeSet):
+            raise TypeError("set_probes: a furniture_amd.probes.ProbeSet, not %r" % type(probe_set).__name__)
+        tab, pts = sensor_table(self.cm, probe_set)
+        planes, adr, num = hull_plane_table(self.cm)
+        self._chk(lib().fsim_set_probes(self._h, len(tab), ctypes.addressof(tab), len(pts), pts.ctypes.data, len(planes),
+                                        planes.ctypes.data if len(planes) else None, adr.ctypes.data, num.ctypes.data))
+        self.probes = probe_set
+
+    def probe_shapes(self):
+        """{key: (shape, dtype)} of probe_distance's outputs (without the n_envs dimension)"""
+        torch = self.torch
+        if self.probes is None:
+            raise FsimError("probe_shapes: no probes set (FSim.set_probes)")
+        p = self.probes.n_probes
+        out = {"probe_distance": ((p,), torch.float32), "probe_geom": ((p,), torch.int32)}
+        if self.probes.gradient:
+            out["probe_gradient"] = ((p, 3), torch.float32)
+        return out
+
+    def probe_distance(self, out=None):
+        """The signed distance of every probe of the probe set in every env (include/fsim_probes.h), for the state sync() leaves -> dict
+        of device tensors: probe_distance (float32 [n, P], metres to the nearest surface, negative inside a solid, dmax = nothing within
+        dmax), probe_geom (int32 [n, P], model geom id as in camera_segmentation, -1 = nothing) and, when the probe set asks for it,
+        probe_gradient (float32 [n, P, 3], the world-frame unit gradient of the distance, (0, 0, 0) = nothing).  out: a dict of such
+        tensors to write into instead of new ones; a key that is there alone is computed alone.  Ordered with torch's current stream
+        both ways."""
+        torch = self.torch
+        if self.probes is None:
+            raise FsimError("probe_distance: no probes set (FSim.set_probes)")
+        want = self.probe_shapes()
+        if out is not None:
+            if not out or any(k not in want for k in out):
+                raise ValueError("probe_distance: out holds %s (of %s)" % (sorted(out), sorted(want)))
+            want = {k: want[k] for k in want if k in out}
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
+                raise ValueError("probe_distance: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
+            res[k] = t
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_probe_distance(self._h, *[res[k].data_ptr() if k in res else None for k in ("probe_distance", "probe_geom", "probe_gradient")]))
         cur.wait_stream(self.torch_stream)
         return res
 

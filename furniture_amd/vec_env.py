@@ -60,6 +60,9 @@ class FurnitureVecEnv:
         if kw.pop("rays", None) is not None:
             raise NotImplementedError("rays= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., rays=RaySet(...)), whose ray outputs stay on the device")
+        if kw.pop("probes", None) is not None:
+            raise NotImplementedError("probes= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., probes=ProbeSet(...)), whose probe outputs stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
