@@ -532,6 +532,32 @@ template <class Emit, bool MESH = false> DEV void np_mpr(const Emit &e, const Sh
   }
 }
 
+// stage 2 of the broadphase, one candidate pair: false => the pair cannot touch.
+// Tighter test for flat / long shapes (a 0.64 x 0.24 x 0.04 table top has a 0.34 m bounding sphere): the distance from
+// the OTHER geom's centre to this box / cylinder (exact point-solid distance) must be within the other geom's
+// bounding radius.  Conservative: never rejects a pair that can touch.
+// d = centre 2 - centre 1; q2 / q3: sizes of geom 1 / geom 2 (the pair record's words 8..10 / 12..14); r1, r2: bounding radii
+DEV bool fs_stage2_near(int t1, int t2, V3 d, const M3 &Ra, const M3 &Rb, f4_t q2, f4_t q3, float margin, float r1, float r2) {
+  bool pass = true;
+  if (t1 != GT_PLANE) {
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+      const int ty = side ? t1 : t2;                       // solid tested
+      const float ro = (side ? r2 : r1) + margin;         // other geom's radius
+      const V3 dw = side ? -d : d;                        // centre(solid) - centre(other)
+      const M3 &R = side ? Ra : Rb;
+      const V3 cl = v3(-(R.m[0] * dw.x + R.m[3] * dw.y + R.m[6] * dw.z), -(R.m[1] * dw.x + R.m[4] * dw.y + R.m[7] * dw.z), -(R.m[2] * dw.x + R.m[5] * dw.y + R.m[8] * dw.z));
+      const f4_t qs = side ? q2 : q3;
+      const V3 sz_ = v3(qs.x, qs.y, qs.z);
+      const V3 e = v3(fmaxf(fabsf(cl.x) - sz_.x, 0.0f), fmaxf(fabsf(cl.y) - sz_.y, 0.0f), fmaxf(fabsf(cl.z) - sz_.z, 0.0f));
+      const float er = fmaxf(sqrtf(cl.x * cl.x + cl.y * cl.y) - sz_.x, 0.0f), ez = fmaxf(fabsf(cl.z) - sz_.y, 0.0f);
+      const float dist2 = ty == GT_BOX ? dot(e, e) : er * er + ez * ez;
+      if ((ty == GT_BOX || ty == GT_CYLINDER) && dist2 > ro * ro) pass = false;
+    }
+  }
+  return pass;
+}
+
 // ---- driver ----------------------------------------------------------------------------------
 #ifdef FSIM_PROFILE
 #define FS_CPROF(slot) do { long long t1c_ = clock64(); if (c.lane == 0) c.I(c.ly.scal)[16 + slot] += (int)((t1c_ - t0c_) >> 4); t0c_ = t1c_; } while (0)
@@ -609,26 +635,8 @@ template <class Ctx> DEV void fs_collide(const Ctx &c) {
       const float margin = q1.x, r1 = q1.z, r2 = q1.w;
       const V3 d = ldv3(L + c.ly.gpos + 3 * g2) - ldv3(L + c.ly.gpos + 3 * g1);
       const M3 Ra = ldm3(L + c.ly.gmat + 9 * g1), Rb = ldm3(L + c.ly.gmat + 9 * g2);
-      pass = i < nA;
-      // tighter test for flat / long shapes (a 0.64 x 0.24 x 0.04 table top has a 0.34 m bounding sphere): the distance from
-      // the OTHER geom's centre to this box / cylinder (exact point-solid distance) must be within the other geom's
-      // bounding radius.  Conservative: never rejects a pair that can touch.
-      if (t1 != GT_PLANE) {
-#pragma unroll
-        for (int side = 0; side < 2; side++) {
-          const int ty = side ? t1 : t2;                       // solid tested
-          const float ro = (side ? r2 : r1) + margin;         // other geom's radius
-          const V3 dw = side ? -d : d;                        // centre(solid) - centre(other)
-          const M3 &R = side ? Ra : Rb;
-          const V3 cl = v3(-(R.m[0] * dw.x + R.m[3] * dw.y + R.m[6] * dw.z), -(R.m[1] * dw.x + R.m[4] * dw.y + R.m[7] * dw.z), -(R.m[2] * dw.x + R.m[5] * dw.y + R.m[8] * dw.z));
-          const f4_t qs = side ? q2 : q3;
-          const V3 sz_ = v3(qs.x, qs.y, qs.z);
-          const V3 e = v3(fmaxf(fabsf(cl.x) - sz_.x, 0.0f), fmaxf(fabsf(cl.y) - sz_.y, 0.0f), fmaxf(fabsf(cl.z) - sz_.z, 0.0f));
-          const float er = fmaxf(sqrtf(cl.x * cl.x + cl.y * cl.y) - sz_.x, 0.0f), ez = fmaxf(fabsf(cl.z) - sz_.y, 0.0f);
-          const float dist2 = ty == GT_BOX ? dot(e, e) : er * er + ez * ez;
-          if ((ty == GT_BOX || ty == GT_CYLINDER) && dist2 > ro * ro) pass = false;
-        }
-      }
+      const bool near2 = fs_stage2_near(t1, t2, d, Ra, Rb, q2, q3, margin, r1, r2);
+      pass = i < nA && near2;
     }
     unsigned long long mask = __ballot(pass);
     int idx = nsurv + __popcll(mask & ((1ull << c.lane) - 1ull));

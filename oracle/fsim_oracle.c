@@ -721,3 +721,16 @@ real osim_cost_at(osim_t *s, const real *qacc) {
 }
 /* signed distance of listed contact i (< 0: penetration), as data.contact[i].dist */
 real osim_contact_dist(osim_t *s, int i) { return (i >= 0 && i < s->ncon) ? s->contact[i].dist : 0.0; }
+/* the narrow phase of one pair, outside any model (see fsim_oracle.h) */
+int osim_narrowphase(int t1, const real *p1, const real *R1, const real *s1, const real *verts1, int n1,
+                     int t2, const real *p2, const real *R2, const real *s2, const real *verts2, int n2, real margin, real out[16][7]) {
+  CPoint cp[16];
+  int swap = t1 > t2;
+  int n = swap ? narrowphase_pair(t2, p2, R2, s2, verts2, n2, t1, p1, R1, s1, verts1, n1, margin, cp)
+               : narrowphase_pair(t1, p1, R1, s1, verts1, n1, t2, p2, R2, s2, verts2, n2, margin, cp);
+  for (int i = 0; i < n && i < 16; i++) {
+    out[i][0] = cp[i].dist;
+    for (int k = 0; k < 3; k++) { out[i][1 + k] = cp[i].pos[k]; out[i][4 + k] = swap ? -cp[i].n[k] : cp[i].n[k]; }
+  }
+  return n;
+}

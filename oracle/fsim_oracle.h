@@ -60,6 +60,15 @@ real osim_row_dot(osim_t *, int i, const real *a);
 real osim_cost_at(osim_t *, const real *qacc);
 void osim_set_solver_kind(osim_t *, int kind); /* 0 = PGS (dual), 1 = Newton (primal, MuJoCo default) */
 
+/* The narrow phase of ONE pair of geoms, with no model behind it: types (MuJoCo's mjtGeom numbers), world positions, row-major rotation
+ * matrices, sizes, and for a convex mesh its hull vertices (geom frame, n of them; NULL / 0 otherwise).  Dispatches exactly as the
+ * collision pass of osim_forward does (the pair is evaluated with the lower type number first; both share one routine) and writes
+ * dist, pos[3], n[3] per contact, the normal pointing from the geom passed first to the geom passed second.  Returns the number of
+ * contacts, or -1 when no routine serves the two types.  Pairs served by the portal routine ignore the margin: they are contacts only
+ * once the shapes interpenetrate. */
+int osim_narrowphase(int t1, const real *p1, const real *R1, const real *s1, const real *verts1, int n1,
+                     int t2, const real *p2, const real *R2, const real *s2, const real *verts2, int n2, real margin, real out[16][7]);
+
 #ifdef __cplusplus
 }
 #endif

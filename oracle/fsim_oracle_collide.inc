@@ -447,6 +447,31 @@ static void add_contact(osim_t *s, int g1, int g2, const CPoint *c, real margin,
   s->ncon++;
 }
 
+/* ---- the narrow phase of ONE pair: geom 1 has the lower type number (the caller orders the pair); verts / n: hull vertices of a G_MESH geom
+ * (geom frame).  Returns the number of contacts written to out (at most 8), or -1 when no routine serves the two types.  collide() and
+ * osim_narrowphase (the per-pair entry the narrow-phase tests call) share this one copy. */
+static int narrowphase_pair(int t1, const real *p1, const real *R1, const real *s1, const real *verts1, int n1,
+                            int t2, const real *p2, const real *R2, const real *s2, const real *verts2, int n2, real margin, CPoint *cp) {
+  if (t1 == G_PLANE && t2 == G_SPHERE) return plane_sphere(p1, R1, p2, s2[0], margin, cp);
+  if (t1 == G_PLANE && t2 == G_BOX) return plane_box(p1, R1, p2, R2, s2, margin, cp);
+  if (t1 == G_PLANE && t2 == G_CYLINDER) return plane_cylinder(p1, R1, p2, R2, s2, margin, cp);
+  if (t1 == G_SPHERE && t2 == G_SPHERE) return sphere_sphere(p1, s1[0], p2, s2[0], margin, cp);
+  if (t1 == G_SPHERE && t2 == G_BOX) return sphere_box(p1, s1[0], p2, R2, s2, margin, cp);
+  if (t1 == G_SPHERE && t2 == G_CYLINDER) return sphere_cylinder(p1, s1[0], p2, R2, s2, margin, cp);
+  if (t1 == G_BOX && t2 == G_BOX) return box_box(p1, R1, s1, p2, R2, s2, margin, cp);
+  if (t1 == G_PLANE && t2 == G_CAPSULE) return plane_capsule(p1, R1, p2, R2, s2, margin, cp);
+  if (t1 == G_PLANE && t2 == G_MESH && verts2 && n2 > 0) return plane_mesh(p1, R1, p2, R2, verts2, n2, margin, cp);
+  if ((t1 == G_CYLINDER && t2 == G_BOX) || (t1 == G_CYLINDER && t2 == G_CYLINDER) ||
+      ((t1 == G_CAPSULE || t2 == G_CAPSULE || t2 == G_MESH) && t1 != G_PLANE && t1 != G_ELLIPSOID && t2 != G_ELLIPSOID &&
+       (t1 != G_MESH || (verts1 && n1 > 0)) && (t2 != G_MESH || (verts2 && n2 > 0)))) {
+    /* sphere / capsule / cylinder / box / mesh against a capsule or a convex mesh: the portal routine with their support functions.
+     * It takes no margin: such a pair is a contact only once the two shapes interpenetrate (the device's np_mpr does the same) */
+    Shape A = {t1, p1, R1, s1, t1 == G_MESH ? verts1 : NULL, t1 == G_MESH ? n1 : 0}, B = {t2, p2, R2, s2, t2 == G_MESH ? verts2 : NULL, t2 == G_MESH ? n2 : 0};
+    return mpr_convex(&A, &B, cp);
+  }
+  return -1;
+}
+
 static void collide(osim_t *s) {
   Model *m = &s->m;
   s->ncon = 0;
@@ -469,26 +494,12 @@ static void collide(osim_t *s) {
       if (dot3(d, n) > m->geom_rbound[g2] + margin) continue;
     }
     CPoint cp[16];
-    int n = 0;
-    if (t1 == G_PLANE && t2 == G_SPHERE) n = plane_sphere(p1, R1, p2, s2[0], margin, cp);
-    else if (t1 == G_PLANE && t2 == G_BOX) n = plane_box(p1, R1, p2, R2, s2, margin, cp);
-    else if (t1 == G_PLANE && t2 == G_CYLINDER) n = plane_cylinder(p1, R1, p2, R2, s2, margin, cp);
-    else if (t1 == G_SPHERE && t2 == G_SPHERE) n = sphere_sphere(p1, s1[0], p2, s2[0], margin, cp);
-    else if (t1 == G_SPHERE && t2 == G_BOX) n = sphere_box(p1, s1[0], p2, R2, s2, margin, cp);
-    else if (t1 == G_SPHERE && t2 == G_CYLINDER) n = sphere_cylinder(p1, s1[0], p2, R2, s2, margin, cp);
-    else if (t1 == G_BOX && t2 == G_BOX) n = box_box(p1, R1, s1, p2, R2, s2, margin, cp);
-    else if (t1 == G_PLANE && t2 == G_CAPSULE) n = plane_capsule(p1, R1, p2, R2, s2, margin, cp);
-    else if (t1 == G_PLANE && t2 == G_MESH && m->mesh_vert && m->geom_meshnum[g2] > 0)
-      n = plane_mesh(p1, R1, p2, R2, m->mesh_vert + 3 * m->geom_meshadr[g2], m->geom_meshnum[g2], margin, cp);
-    else if ((t1 == G_CYLINDER && t2 == G_BOX) || (t1 == G_CYLINDER && t2 == G_CYLINDER) ||
-             ((t1 == G_CAPSULE || t2 == G_CAPSULE || t2 == G_MESH) && t1 != G_PLANE && t1 != G_ELLIPSOID && t2 != G_ELLIPSOID &&
-              (t1 != G_MESH || (m->mesh_vert && m->geom_meshnum[g1] > 0)) && (t2 != G_MESH || (m->mesh_vert && m->geom_meshnum[g2] > 0)))) {
-      /* sphere / capsule / cylinder / box / mesh against a capsule or a convex mesh: the portal routine with their support functions */
-      Shape A = {t1, p1, R1, s1, NULL, 0}, B = {t2, p2, R2, s2, NULL, 0};
-      if (t1 == G_MESH) { A.verts = m->mesh_vert + 3 * m->geom_meshadr[g1]; A.nvert = m->geom_meshnum[g1]; }
-      if (t2 == G_MESH) { B.verts = m->mesh_vert + 3 * m->geom_meshadr[g2]; B.nvert = m->geom_meshnum[g2]; }
-      n = mpr_convex(&A, &B, cp);
-    } else { fprintf(stderr, "fsim_oracle: no narrow-phase routine for geom types %d x %d (the model compiler refuses such pairs)\n", t1, t2); abort(); }
+    const real *v1 = NULL, *v2 = NULL;
+    int n1 = 0, n2 = 0;
+    if (t1 == G_MESH && m->mesh_vert) { v1 = m->mesh_vert + 3 * m->geom_meshadr[g1]; n1 = m->geom_meshnum[g1]; }
+    if (t2 == G_MESH && m->mesh_vert) { v2 = m->mesh_vert + 3 * m->geom_meshadr[g2]; n2 = m->geom_meshnum[g2]; }
+    int n = narrowphase_pair(t1, p1, R1, s1, v1, n1, t2, p2, R2, s2, v2, n2, margin, cp);
+    if (n < 0) { fprintf(stderr, "fsim_oracle: no narrow-phase routine for geom types %d x %d (the model compiler refuses such pairs)\n", t1, t2); abort(); }
     for (int i = 0; i < n; i++) add_contact(s, g1, g2, &cp[i], margin, gap);
   }
 }

@@ -54,6 +54,40 @@ def lib():
     return _LIB
 
 
+_NP_LIBS = {}
+
+
+def narrowphase(t1, p1, R1, s1, t2, p2, R2, s2, margin, verts1=None, verts2=None, dtype=np.float64):
+    """osim_narrowphase over N pairs of one type combination: p (N, 3), R (N, 3, 3), s (N, 3), margin scalar or (N,), verts (V, 3) hull
+    vertices shared by the N pairs.  Returns (count (N,), contacts (N, 16, 7): dist, pos, normal), float64 whatever the build.
+    dtype float64: the checker; float32: the control build libfsim_cpu32.so (the same source with real = float)."""
+    dtype = np.dtype(dtype)
+    if dtype not in _NP_LIBS:
+        if dtype == np.float64:
+            L = lib()
+        else:
+            build()
+            L = ctypes.CDLL(os.path.join(_HERE, "libfsim_cpu32.so"))
+        L.osim_narrowphase.restype = ctypes.c_int
+        L.osim_narrowphase.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int] + \
+            [ctypes.c_double if dtype == np.float64 else ctypes.c_float, ctypes.c_void_p]
+        _NP_LIBS[dtype] = L
+    L = _NP_LIBS[dtype]
+    n = len(p1)
+    a = [np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(n, -1), dtype=dtype) for x in (p1, R1, s1, p2, R2, s2)]
+    v = [None if x is None else np.ascontiguousarray(x, dtype=dtype) for x in (verts1, verts2)]
+    vp = [None if x is None else x.ctypes.data for x in v]
+    vn = [0 if x is None else len(x) for x in v]
+    mg = np.broadcast_to(np.asarray(margin, dtype=np.float64), (n,))
+    cnt, out = np.zeros(n, dtype=np.int32), np.zeros((n, 16, 7), dtype=dtype)
+    ptr = [x.ctypes.data for x in a]
+    st = [x.strides[0] for x in a]
+    for i in range(n):
+        cnt[i] = L.osim_narrowphase(int(t1), ptr[0] + i * st[0], ptr[1] + i * st[1], ptr[2] + i * st[2], vp[0], vn[0],
+                                    int(t2), ptr[3] + i * st[3], ptr[4] + i * st[4], ptr[5] + i * st[5], vp[1], vn[1], float(mg[i]), out[i].ctypes.data)
+    return cnt, out.astype(np.float64)
+
+
 class OracleCapacity(RuntimeError):
     """a substep had more contacts / constraint rows than the checker holds"""
 
