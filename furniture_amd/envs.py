@@ -362,9 +362,10 @@ class FurnitureBatchEnv:
     flow = None
     rays = None
     probes = None
+    pairs = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -398,7 +399,12 @@ class FurnitureBatchEnv:
         [n, P], metres from each probe point of the set's sensors to the nearest surface, negative inside a solid, the sensor's dmax where
         nothing is within it), probe_geom (int32 [n, P], model geom id as in camera_segmentation, -1 = nothing) and, with gradient=True,
         probe_gradient (float32 [n, P, 3], the world-frame unit gradient of the distance, (0, 0, 0) = nothing), from one
-        fsim_probe_distance call."""
+        fsim_probe_distance call.
+        pairs: a furniture_amd.pairs.PairSet (needs no cameras, rays or probes) -- the observations then also hold pair_distance (float32
+        [n, S], metres between the nearest geoms of each sensor's two sides, negative when they overlap, the sensor's dmax where nothing is
+        within it), pair_geoms (int32 [n, S, 2], the model geom ids of the two as in camera_segmentation, -1 = nothing) and, with
+        fromto=True / normal=True, pair_fromto (float32 [n, S, 6], the two nearest points) and pair_normal (float32 [n, S, 3], the unit
+        direction from side a to side b), from one fsim_pair_distance call."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -417,6 +423,9 @@ class FurnitureBatchEnv:
         if probes is not None:
             from .probes import check as check_probes
             check_probes(probes)
+        if pairs is not None:
+            from .pairs import check as check_pairs
+            check_pairs(pairs)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -541,6 +550,10 @@ class FurnitureBatchEnv:
         if probes is not None:  # (without probes: no allocation, no launch, the same observation dict)
             self.sim.set_probes(probes)
             self._probe_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.probe_shapes().items()}
+        self.pairs = pairs
+        if pairs is not None:  # (without pairs: no allocation, no launch, the same observation dict)
+            self.sim.set_pairs(pairs)
+            self._pair_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.pair_shapes().items()}
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -598,6 +611,14 @@ class FurnitureBatchEnv:
             sp.append(("probe_geom", spaces.Box(-1, self.model.ngeom - 1, shape=(r,), dtype=np.int32)))
             if self.probes.gradient:
                 sp.append(("probe_gradient", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
+        if self.pairs is not None:
+            r = self.pairs.n_sensors
+            sp.append(("pair_distance", spaces.Box(-np.inf, max(k.dmax for k in self.pairs.sensors), shape=(r,), dtype=np.float32)))
+            sp.append(("pair_geoms", spaces.Box(-1, self.model.ngeom - 1, shape=(r, 2), dtype=np.int32)))
+            if self.pairs.fromto:
+                sp.append(("pair_fromto", spaces.Box(-np.inf, np.inf, shape=(r, 6), dtype=np.float32)))
+            if self.pairs.normal:
+                sp.append(("pair_normal", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -613,7 +634,8 @@ class FurnitureBatchEnv:
         shaded images when they are set (from one fsim_render_normals call, after the others: one more ray pass when there are any) and
         the flow / velocity images when they are set (from one fsim_render_flow call, last: again one more ray pass when there are any) and
         the ray sensors' outputs when a ray set is given (from one fsim_cast_rays call) and the distance probes' outputs when a probe set
-        is given (from one fsim_probe_distance call)"""
+        is given (from one fsim_probe_distance call) and the pair sensors' outputs when a pair set is given (from one fsim_pair_distance
+        call)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -643,6 +665,8 @@ class FurnitureBatchEnv:
             out.update(self.sim.cast_rays(out=self._ray_out))
         if self.probes is not None:  # one fsim_probe_distance call; independent of the cameras and the rays
             out.update(self.sim.probe_distance(out=self._probe_out))
+        if self.pairs is not None:  # one fsim_pair_distance call; independent of the cameras, the rays and the probes
+            out.update(self.sim.pair_distance(out=self._pair_out))
         return out
 
     def _at_points(self, image):
@@ -988,7 +1012,7 @@ class _SingleEnv:
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
                                          point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays,
-                                         probes=old.probes)
+                                         probes=old.probes, pairs=old.pairs)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

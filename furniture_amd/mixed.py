@@ -59,6 +59,9 @@ class FurnitureMixedBatchEnv:
         if kw.pop("probes", None) is not None:
             raise NotImplementedError("probes= is not supported by the mixed-furniture batch (one probe set per FurnitureBatchEnv): "
                                       "make one FurnitureBatchEnv per furniture instead")
+        if kw.pop("pairs", None) is not None:
+            raise NotImplementedError("pairs= is not supported by the mixed-furniture batch (one pair set per FurnitureBatchEnv): "
+                                      "make one FurnitureBatchEnv per furniture instead")
         cfg = config if config is not None else make_config()
         for key, v in kw.items():
             setattr(cfg, key, v)

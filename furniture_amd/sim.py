@@ -67,6 +67,11 @@ class FsimProbeSensor(ctypes.Structure):
                 ("first_probe", ctypes.c_int32), ("n_probes", ctypes.c_int32), ("exclude", ctypes.c_uint32 * 3)]
 
 
+class FsimPairSensor(ctypes.Structure):
+    """fsim_pair_sensor_t (include/fsim_pairs.h)"""
+    _fields_ = [("a", ctypes.c_uint32 * 3), ("b", ctypes.c_uint32 * 3), ("dmax", ctypes.c_float)]
+
+
 def library_path():
     return _LIBPATH
 
@@ -74,7 +79,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -184,6 +189,8 @@ def lib():
         L.fsim_cast_rays.argtypes = [ctypes.c_void_p] * 4
         L.fsim_set_probes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fsim_probe_distance.argtypes = [ctypes.c_void_p] * 4
+        L.fsim_set_pairs.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.fsim_pair_distance.argtypes = [ctypes.c_void_p] * 5
         _LIB = L
     return _LIB
 
@@ -211,6 +218,8 @@ FLOW_SYMBOLS = ["fsim_render_flow"]
 RAY_SYMBOLS = ["fsim_set_rays", "fsim_cast_rays"]
 # the distance-probe entry points: a header of their own (include/fsim_probes.h), exported by the same library
 PROBE_SYMBOLS = ["fsim_set_probes", "fsim_probe_distance"]
+# the geom-pair distance entry points: a header of their own (include/fsim_pairs.h), exported by the same library
+PAIR_SYMBOLS = ["fsim_set_pairs", "fsim_pair_distance"]
 
 
 def preassembled_rows(model, preassembled):
@@ -784,6 +793,63 @@ class FSim:
         cur = torch.cuda.current_stream(self.device)
         self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
         self._chk(lib().fsim_probe_distance(self._h, *[res[k].data_ptr() if k in res else None for k in ("probe_distance", "probe_geom", "probe_gradient")]))
+        cur.wait_stream(self.torch_stream)
+        return res
+
+    # -- geom-pair distance sensors (include/fsim_pairs.h, furniture_amd/pairs.py) ---------------------------------------------------------
+    pairs = None
+
+    def set_pairs(self, pair_set):
+        """Replace the handle's pair set (a furniture_amd.pairs.PairSet; None clears it); checked on the host first, then by the
+        library.  Independent of the cameras, the rays and the probes: needs and disturbs none of them."""
+        from .pairs import PairSet, sensor_table
+        if pair_set is None:
+            self._chk(lib().fsim_set_pairs(self._h, 0, None))
+            self.pairs = None
+            return
+        if not isinstance(pair_set, PairSet):
+            raise TypeError("set_pairs: a furniture_amd.pairs.PairSet, not %r" % type(pair_set).__name__)
+        tab = sensor_table(self.cm, pair_set)
+        self._chk(lib().fsim_set_pairs(self._h, len(tab), ctypes.addressof(tab)))
+        self.pairs = pair_set
+
+    def pair_shapes(self):
+        """{key: (shape, dtype)} of pair_distance's outputs (without the n_envs dimension)"""
+        torch = self.torch
+        if self.pairs is None:
+            raise FsimError("pair_shapes: no pair set (FSim.set_pairs)")
+        k = self.pairs.n_sensors
+        out = {"pair_distance": ((k,), torch.float32), "pair_geoms": ((k, 2), torch.int32)}
+        if self.pairs.fromto:
+            out["pair_fromto"] = ((k, 6), torch.float32)
+        if self.pairs.normal:
+            out["pair_normal"] = ((k, 3), torch.float32)
+        return out
+
+    def pair_distance(self, out=None):
+        """The distance of every sensor of the pair set in every env (include/fsim_pairs.h), for the state sync() leaves -> dict of
+        device tensors: pair_distance (float32 [n, S], metres between the nearest geoms of the sensor's two sides, negative when they
+        overlap, dmax = nothing within dmax), pair_geoms (int32 [n, S, 2], the model geom ids of the two as in camera_segmentation,
+        -1 = nothing) and, when the pair set asks for them, pair_fromto (float32 [n, S, 6], the nearest points: on side a, then on side b)
+        and pair_normal (float32 [n, S, 3], the unit direction from a to b; (0, 0, 0) = nothing).  out: a dict of such tensors to write
+        into instead of new ones; a key that is there alone is computed alone.  Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if self.pairs is None:
+            raise FsimError("pair_distance: no pair set (FSim.set_pairs)")
+        want = self.pair_shapes()
+        if out is not None:
+            if not out or any(k not in want for k in out):
+                raise ValueError("pair_distance: out holds %s (of %s)" % (sorted(out), sorted(want)))
+            want = {k: want[k] for k in want if k in out}
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
+                raise ValueError("pair_distance: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
+            res[k] = t
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_pair_distance(self._h, *[res[k].data_ptr() if k in res else None for k in ("pair_distance", "pair_geoms", "pair_fromto", "pair_normal")]))
         cur.wait_stream(self.torch_stream)
         return res
 

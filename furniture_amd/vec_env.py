@@ -63,6 +63,9 @@ class FurnitureVecEnv:
         if kw.pop("probes", None) is not None:
             raise NotImplementedError("probes= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., probes=ProbeSet(...)), whose probe outputs stay on the device")
+        if kw.pop("pairs", None) is not None:
+            raise NotImplementedError("pairs= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., pairs=PairSet(...)), whose pair outputs stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
