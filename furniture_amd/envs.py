@@ -363,9 +363,10 @@ class FurnitureBatchEnv:
     rays = None
     probes = None
     pairs = None
+    frames = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -404,7 +405,11 @@ class FurnitureBatchEnv:
         [n, S], metres between the nearest geoms of each sensor's two sides, negative when they overlap, the sensor's dmax where nothing is
         within it), pair_geoms (int32 [n, S, 2], the model geom ids of the two as in camera_segmentation, -1 = nothing) and, with
         fromto=True / normal=True, pair_fromto (float32 [n, S, 6], the two nearest points) and pair_normal (float32 [n, S, 3], the unit
-        direction from side a to side b), from one fsim_pair_distance call."""
+        direction from side a to side b), from one fsim_pair_distance call.
+        frames: a furniture_amd.frames.FrameSet (needs none of the others) -- the observations then also hold frame_pos (float32
+        [n, S, 3], each sensor's frame origin in its reference frame, metres), frame_quat (float32 [n, S, 4], wxyz, its orientation in the
+        reference frame) and, with velocity=True / jacobian=True, frame_vel (float32 [n, S, 6], the rate of frame_pos and the relative
+        angular velocity) and frame_jac (float32 [n, S, 6, nv], frame_vel = frame_jac @ qvel), from one fsim_frame_state call."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -426,6 +431,9 @@ class FurnitureBatchEnv:
         if pairs is not None:
             from .pairs import check as check_pairs
             check_pairs(pairs)
+        if frames is not None:
+            from .frames import check as check_frames
+            check_frames(frames)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -554,6 +562,10 @@ class FurnitureBatchEnv:
         if pairs is not None:  # (without pairs: no allocation, no launch, the same observation dict)
             self.sim.set_pairs(pairs)
             self._pair_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.pair_shapes().items()}
+        self.frames = frames
+        if frames is not None:  # (without frames: no allocation, no launch, the same observation dict)
+            self.sim.set_frames(frames)
+            self._frame_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.frame_shapes().items()}
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -619,6 +631,14 @@ class FurnitureBatchEnv:
                 sp.append(("pair_fromto", spaces.Box(-np.inf, np.inf, shape=(r, 6), dtype=np.float32)))
             if self.pairs.normal:
                 sp.append(("pair_normal", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
+        if self.frames is not None:
+            r = self.frames.n_sensors
+            sp.append(("frame_pos", spaces.Box(-np.inf, np.inf, shape=(r, 3), dtype=np.float32)))
+            sp.append(("frame_quat", spaces.Box(-np.inf, np.inf, shape=(r, 4), dtype=np.float32)))  # (a unit quaternion up to float32 rounding)
+            if self.frames.velocity:
+                sp.append(("frame_vel", spaces.Box(-np.inf, np.inf, shape=(r, 6), dtype=np.float32)))
+            if self.frames.jacobian:
+                sp.append(("frame_jac", spaces.Box(-np.inf, np.inf, shape=(r, 6, self.model.nv), dtype=np.float32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -635,7 +655,7 @@ class FurnitureBatchEnv:
         the flow / velocity images when they are set (from one fsim_render_flow call, last: again one more ray pass when there are any) and
         the ray sensors' outputs when a ray set is given (from one fsim_cast_rays call) and the distance probes' outputs when a probe set
         is given (from one fsim_probe_distance call) and the pair sensors' outputs when a pair set is given (from one fsim_pair_distance
-        call)"""
+        call) and the frame sensors' outputs when a frame set is given (from one fsim_frame_state call)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -667,6 +687,8 @@ class FurnitureBatchEnv:
             out.update(self.sim.probe_distance(out=self._probe_out))
         if self.pairs is not None:  # one fsim_pair_distance call; independent of the cameras, the rays and the probes
             out.update(self.sim.pair_distance(out=self._pair_out))
+        if self.frames is not None:  # one fsim_frame_state call; independent of all the others
+            out.update(self.sim.frame_state(out=self._frame_out))
         return out
 
     def _at_points(self, image):
@@ -1012,7 +1034,7 @@ class _SingleEnv:
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
                                          point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays,
-                                         probes=old.probes, pairs=old.pairs)
+                                         probes=old.probes, pairs=old.pairs, frames=old.frames)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

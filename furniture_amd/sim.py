@@ -72,6 +72,16 @@ class FsimPairSensor(ctypes.Structure):
     _fields_ = [("a", ctypes.c_uint32 * 3), ("b", ctypes.c_uint32 * 3), ("dmax", ctypes.c_float)]
 
 
+class FsimFrame(ctypes.Structure):
+    """fsim_frame_t (include/fsim_frames.h)"""
+    _fields_ = [("body", ctypes.c_int32), ("pos", ctypes.c_float * 3), ("quat", ctypes.c_float * 4)]
+
+
+class FsimFrameSensor(ctypes.Structure):
+    """fsim_frame_sensor_t (include/fsim_frames.h)"""
+    _fields_ = [("frame", FsimFrame), ("ref", FsimFrame)]
+
+
 def library_path():
     return _LIBPATH
 
@@ -79,7 +89,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -191,6 +201,8 @@ def lib():
         L.fsim_probe_distance.argtypes = [ctypes.c_void_p] * 4
         L.fsim_set_pairs.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.fsim_pair_distance.argtypes = [ctypes.c_void_p] * 5
+        L.fsim_set_frames.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.fsim_frame_state.argtypes = [ctypes.c_void_p] * 5
         _LIB = L
     return _LIB
 
@@ -220,6 +232,8 @@ RAY_SYMBOLS = ["fsim_set_rays", "fsim_cast_rays"]
 PROBE_SYMBOLS = ["fsim_set_probes", "fsim_probe_distance"]
 # the geom-pair distance entry points: a header of their own (include/fsim_pairs.h), exported by the same library
 PAIR_SYMBOLS = ["fsim_set_pairs", "fsim_pair_distance"]
+# the frame-sensor entry points: a header of their own (include/fsim_frames.h), exported by the same library
+FRAME_SYMBOLS = ["fsim_set_frames", "fsim_frame_state"]
 
 
 def preassembled_rows(model, preassembled):
@@ -850,6 +864,63 @@ class FSim:
         cur = torch.cuda.current_stream(self.device)
         self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
         self._chk(lib().fsim_pair_distance(self._h, *[res[k].data_ptr() if k in res else None for k in ("pair_distance", "pair_geoms", "pair_fromto", "pair_normal")]))
+        cur.wait_stream(self.torch_stream)
+        return res
+
+    # -- body and site frame sensors with their Jacobians (include/fsim_frames.h, furniture_amd/frames.py) --------------------------------
+    frames = None
+
+    def set_frames(self, frame_set):
+        """Replace the handle's frame set (a furniture_amd.frames.FrameSet; None clears it); checked on the host first, then by the
+        library.  Independent of the cameras, the rays, the probes and the pairs: needs and disturbs none of them."""
+        from .frames import FrameSet, sensor_table
+        if frame_set is None:
+            self._chk(lib().fsim_set_frames(self._h, 0, None))
+            self.frames = None
+            return
+        if not isinstance(frame_set, FrameSet):
+            raise TypeError("set_frames: a furniture_amd.frames.FrameSet, not %r" % type(frame_set).__name__)
+        tab = sensor_table(self.cm, frame_set)
+        self._chk(lib().fsim_set_frames(self._h, len(tab), ctypes.addressof(tab)))
+        self.frames = frame_set
+
+    def frame_shapes(self):
+        """{key: (shape, dtype)} of frame_state's outputs (without the n_envs dimension)"""
+        torch = self.torch
+        if self.frames is None:
+            raise FsimError("frame_shapes: no frame set (FSim.set_frames)")
+        k = self.frames.n_sensors
+        out = {"frame_pos": ((k, 3), torch.float32), "frame_quat": ((k, 4), torch.float32)}
+        if self.frames.velocity:
+            out["frame_vel"] = ((k, 6), torch.float32)
+        if self.frames.jacobian:
+            out["frame_jac"] = ((k, 6, self.cm.nv), torch.float32)
+        return out
+
+    def frame_state(self, out=None):
+        """The state of every sensor of the frame set in every env (include/fsim_frames.h), for the state sync() leaves -> dict of device
+        tensors: frame_pos (float32 [n, S, 3], the frame's origin in its reference frame, metres), frame_quat (float32 [n, S, 4], wxyz,
+        its orientation in the reference frame) and, when the frame set asks for them, frame_vel (float32 [n, S, 6], the time derivative
+        of frame_pos and the relative angular velocity, in the reference frame) and frame_jac (float32 [n, S, 6, nv], frame_vel =
+        frame_jac @ qvel).  out: a dict of such tensors to write into instead of new ones; a key that is there alone is computed alone.
+        Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if self.frames is None:
+            raise FsimError("frame_state: no frame set (FSim.set_frames)")
+        want = self.frame_shapes()
+        if out is not None:
+            if not out or any(k not in want for k in out):
+                raise ValueError("frame_state: out holds %s (of %s)" % (sorted(out), sorted(want)))
+            want = {k: want[k] for k in want if k in out}
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
+                raise ValueError("frame_state: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
+            res[k] = t
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_frame_state(self._h, *[res[k].data_ptr() if k in res else None for k in ("frame_pos", "frame_quat", "frame_vel", "frame_jac")]))
         cur.wait_stream(self.torch_stream)
         return res
 

@@ -66,6 +66,9 @@ class FurnitureVecEnv:
         if kw.pop("pairs", None) is not None:
             raise NotImplementedError("pairs= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., pairs=PairSet(...)), whose pair outputs stay on the device")
+        if kw.pop("frames", None) is not None:
+            raise NotImplementedError("frames= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., frames=FrameSet(...)), whose frame outputs stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
