@@ -859,93 +859,126 @@ template <class Ctx, bool ADD = false> DEV void fs_hessian(const Ctx &c, const S
 template <int J> DEV float fs_rowbc(float v) { // value of lane J of the caller's 16-lane row, in every lane of that row
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x150 + J, 0xf, 0xf, true));
 }
-struct RowBcast { // row phase: lane `pos` of each 16-lane row (DPP row_newbcast)
-  template <int J> DEV float get(float v) const { return fs_rowbc<J>(v); }
-};
-struct LaneBcast { // big phase: lane first + J of the wave (v_readlane, wave-uniform source)
-  int first;
-  template <int J> DEV float get(float v) const { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), first + J)); }
-};
+// a[k] += w * (lane J's a[k]) for N consecutive columns: the trailing update of pivot J.  The broadcast rides on the multiply-add's own source operand
+// (v_fmac_f32 with a DPP source: one instruction per column, one fused multiply-add per element as before), where a v_mov_b32_dpp per column plus a
+// v_pk_fma_f32 per column pair was 1.5 -- the compiler does not fold a DPP move into a multiply-accumulate, hence the assembly.  What the compiler
+// cannot see in there it is given by hand: a VALU write of a register needs two wait states before a DPP read of it, so the block opens with s_nop 1
+// (a register copy placed right in front of it would otherwise be read too early); no column is both written and read inside a block; and the block
+// lasts at least three instructions after its FIRST column, the only one the code behind it reads through DPP (the next pivot's diagonal).
+#define FS_FMAC_BC(k) "v_fmac_f32_dpp %" #k ", %" #k ", %[w] row_newbcast:%[j] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+typedef float fs_f2 __attribute__((ext_vector_type(2)));
+// (the row lives in NLOC / 2 two-float vectors: a plain float array is turned into ONE 16-register value by the compiler, and every branch of
+//  the sweeps then copies the whole of it)
+#define FS_ROW(A, k) ((A)[(k) >> 1][(k) & 1])
+template <int J, int K0, int N, int NLOC> DEV void fs_rowbc_fmac(fs_f2 (&A)[NLOC / 2], const float w) { // columns K0 .. K0 + N - 1
+  static_assert(N >= 1 && N <= 8 && K0 + N <= NLOC, "one block is at most eight columns");
+  float a[8];
+#pragma unroll
+  for (int i = 0; i < N; i++) a[i] = FS_ROW(A, K0 + i);
+  if constexpr (N == 1) asm("s_nop 1\n\t" FS_FMAC_BC(0) "s_nop 1" : "+v"(a[0]) : [w] "v"(w), [j] "n"(J));
+  else if constexpr (N == 2) asm("s_nop 1\n\t" FS_FMAC_BC(0) FS_FMAC_BC(1) "s_nop 0" : "+v"(a[0]), "+v"(a[1]) : [w] "v"(w), [j] "n"(J));
+  else if constexpr (N == 3) asm("s_nop 1\n\t" FS_FMAC_BC(0) FS_FMAC_BC(1) FS_FMAC_BC(2) : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]) : [w] "v"(w), [j] "n"(J));
+  else if constexpr (N == 4) asm("s_nop 1\n\t" FS_FMAC_BC(0) FS_FMAC_BC(1) FS_FMAC_BC(2) FS_FMAC_BC(3) : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : [w] "v"(w), [j] "n"(J));
+  else if constexpr (N == 5) asm("s_nop 1\n\t" FS_FMAC_BC(0) FS_FMAC_BC(1) FS_FMAC_BC(2) FS_FMAC_BC(3) FS_FMAC_BC(4)
+                                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]) : [w] "v"(w), [j] "n"(J));
+  else if constexpr (N == 6) asm("s_nop 1\n\t" FS_FMAC_BC(0) FS_FMAC_BC(1) FS_FMAC_BC(2) FS_FMAC_BC(3) FS_FMAC_BC(4) FS_FMAC_BC(5)
+                                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]) : [w] "v"(w), [j] "n"(J));
+  else if constexpr (N == 7) asm("s_nop 1\n\t" FS_FMAC_BC(0) FS_FMAC_BC(1) FS_FMAC_BC(2) FS_FMAC_BC(3) FS_FMAC_BC(4) FS_FMAC_BC(5) FS_FMAC_BC(6)
+                                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]) : [w] "v"(w), [j] "n"(J));
+  else asm("s_nop 1\n\t" FS_FMAC_BC(0) FS_FMAC_BC(1) FS_FMAC_BC(2) FS_FMAC_BC(3) FS_FMAC_BC(4) FS_FMAC_BC(5) FS_FMAC_BC(6) FS_FMAC_BC(7)
+           : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]) : [w] "v"(w), [j] "n"(J));
+#pragma unroll
+  for (int i = 0; i < N; i++) FS_ROW(A, K0 + i) = a[i];
+}
+#undef FS_FMAC_BC
 
 // One phase: every lane owns row `l` (position `pos` in its group, which starts at position pos - l) of a symmetric matrix;
 // steps = largest group fill in the wave (uniform).  A[q] = row entries by position.  Unoccupied positions carry a unit
 // diagonal (set by the caller), so no per-step "is this pivot live" predicate exists; the lane-role tests (pivot / below /
 // above) are single-use compares against `pos` -- kept that way on purpose: when the forward and the backward sweep shared
 // them the compiler held 2 x NLOC lane masks in SGPR pairs, spilled them to VGPR lanes and a third of this routine's
-// instructions were v_readlane reloads of masks.
-typedef float fs_f2 __attribute__((ext_vector_type(2)));
-// (the row lives in NLOC / 2 two-float vectors so that the trailing update is v_pk_fma_f32 on register pairs the allocator keeps
-//  aligned -- with a plain float array the SLP-packed update paid 2.5 v_mov per packed FMA to build the pairs)
-#define FS_ROW(A, k) ((A)[(k) >> 1][(k) & 1])
-template <int NLOC, int JJ, class BC> struct FsCholStep {
-  DEV static void fwd(fs_f2 (&A)[NLOC / 2], float &b, float &mydinv, float &dmin, const int pos, const int steps, const BC &bc) {
+// instructions were v_readlane reloads of masks.  (`pos` is threaded through the steps as ONE variable that an empty asm
+// statement redefines in place at every step: a fresh copy per step, as it used to be, cost a v_mov_b32 per pivot and sweep.)
+template <int NLOC, int JJ> struct FsCholStep {
+  DEV static void fwd(fs_f2 (&A)[NLOC / 2], float &b, float &mydinv, float &dmin, int &pos, const int steps) {
     if (JJ < steps) {
       const float ajj = FS_ROW(A, JJ);
-      const float d = bc.template get<JJ>(ajj);
+      const float d = fs_rowbc<JJ>(ajj);
+      // (ties this step's lane-role compares to this step -- see the note above -- and to its FIRST broadcast, so that they can issue in the shadow
+      //  of the reciprocal square root instead of behind the second broadcast, where each paid hazard nops in front of its select)
+      asm volatile("" : "+v"(pos) : "v"(d));
       dmin = fminf(dmin, d);
       const float rinv = rsqrtf(fmaxf(d, 1e-30f));
       // forward substitution, column form: y_j = b_j / L_jj, then b_l -= L[l][j] y_j below the pivot
-      const float yj = bc.template get<JJ>(b * rinv);
+      const float yj = fs_rowbc<JJ>(b * rinv);
       const float lij = ajj * rinv; // L[l][j] for pos > j
-      int pj = pos;
-      asm volatile("" : "+v"(pj) : "v"(yj)); // (ties this step's lane-role compares to this step: see the note above)
-      const bool below = pj > JJ;
-      b = pj == JJ ? yj : b;
-      mydinv = pj == JJ ? rinv : mydinv;
+      const bool below = pos > JJ;
+      b = pos == JJ ? yj : b;
+      mydinv = pos == JJ ? rinv : mydinv;
       b = below ? __builtin_fmaf(-lij, yj, b) : b;
       const float w = below ? -lij * rinv : 0.0f; // A[l][k] -= L[l][j] L[k][j] = A[l][j] A[j][k] / d
-      const fs_f2 w2 = {w, w};
-      if ((JJ + 1) & 1) { // odd first column: scalar
-        if (JJ + 1 < NLOC) FS_ROW(A, JJ + 1) = __builtin_fmaf(w, bc.template get<JJ>(FS_ROW(A, JJ + 1)), FS_ROW(A, JJ + 1));
+      // (columns >= steps are zero in every lane that is a pivot, so how far beyond `steps` a block reaches changes nothing)
+      constexpr int N0 = NLOC - 1 - JJ < 8 ? NLOC - 1 - JJ : 8, N1 = NLOC - 1 - JJ - N0;
+      if constexpr (N0 > 0) fs_rowbc_fmac<JJ, JJ + 1, N0, NLOC>(A, w);
+      if constexpr (N1 > 0) {
+        if (JJ + 1 + N0 < steps) fs_rowbc_fmac<JJ, JJ + 1 + N0, N1, NLOC>(A, w);
       }
-#pragma unroll
-      for (int kk = (JJ + 2) >> 1; kk < NLOC / 2; kk++) {
-        if (((kk - ((JJ + 2) >> 1)) & 1) == 0 && 2 * kk >= steps) break;
-        const fs_f2 t = {bc.template get<JJ>(A[kk].x), bc.template get<JJ>(A[kk].y)};
-        A[kk] = __builtin_elementwise_fma(w2, t, A[kk]);
-      }
-      FsCholStep<NLOC, JJ + 1, BC>::fwd(A, b, mydinv, dmin, pos, steps, bc);
+      FsCholStep<NLOC, JJ + 1>::fwd(A, b, mydinv, dmin, pos, steps);
     }
   }
   // backward: L' p = y.  L[j][l] = A[l][j] * dinv_l for l < j (lane l's row as it was when l was the pivot)
-  DEV static void bwd(const fs_f2 (&A)[NLOC / 2], float &b, const float mydinv, const int pos, const int steps, const BC &bc) {
+  DEV static void bwd(const fs_f2 (&A)[NLOC / 2], float &b, const float mydinv, int &pos, const int steps) {
     constexpr int J = NLOC - 1 - JJ;
     if (J < steps) {
-      const float pj = bc.template get<J>(b * mydinv);
-      int pk = pos;
-      asm volatile("" : "+v"(pk) : "v"(pj));
-      b = pk == J ? pj : b;
-      b = pk < J ? __builtin_fmaf(-FS_ROW(A, J) * mydinv, pj, b) : b;
+      asm volatile("" : "+v"(pos) : "v"(b)); // (as in the forward sweep: tied to the step's input, the compares issue ahead of the broadcast)
+      const float pj = fs_rowbc<J>(b * mydinv);
+      b = pos == J ? pj : b;
+      b = pos < J ? __builtin_fmaf(-FS_ROW(A, J) * mydinv, pj, b) : b;
     }
-    FsCholStep<NLOC, JJ + 1, BC>::bwd(A, b, mydinv, pos, steps, bc);
+    FsCholStep<NLOC, JJ + 1>::bwd(A, b, mydinv, pos, steps);
   }
 };
-template <int NLOC, class BC> struct FsCholStep<NLOC, NLOC, BC> {
-  DEV static void fwd(fs_f2 (&)[NLOC / 2], float &, float &, float &, const int, const int, const BC &) {}
-  DEV static void bwd(const fs_f2 (&)[NLOC / 2], float &, const float, const int, const int, const BC &) {}
+template <int NLOC> struct FsCholStep<NLOC, NLOC> {
+  DEV static void fwd(fs_f2 (&)[NLOC / 2], float &, float &, float &, int &, const int) {}
+  DEV static void bwd(const fs_f2 (&)[NLOC / 2], float &, const float, int &, const int) {}
+};
+
+// A[q] = the unit diagonal of a lane without a dof, e[q] inside the lane's island, 0 elsewhere
+template <int NLOC, int Q> struct FsRowSelect {
+  DEV static void run(fs_f2 (&A)[NLOC / 2], const float (&e)[NLOC], const int diag, const int p0, const unsigned nq) {
+    FS_ROW(A, Q) = Q == diag ? 1.0f : ((unsigned)(Q - p0) < nq ? e[Q] : 0.0f);
+    FsRowSelect<NLOC, Q + 1>::run(A, e, diag, p0, nq);
+  }
+};
+template <int NLOC> struct FsRowSelect<NLOC, NLOC> {
+  DEV static void run(fs_f2 (&)[NLOC / 2], const float (&)[NLOC], const int, const int, const unsigned) {}
 };
 
 // dof: the dof this lane owns in this phase (< 0: none); pos / steps as above; writes p[dof].  returns the lane's bad flag
-template <int NLOC, class BC, class Ctx> DEV int fs_chol_phase(const Ctx &c, int mp, const int dof, const int pos, const int steps, const BC &bc) {
-  static_assert(NLOC % 2 == 0, "rows are stored as float pairs");
+template <int NLOC, class Ctx> DEV int fs_chol_phase(const Ctx &c, int mp, const int dof, const int pos, const int steps) {
+  static_assert(NLOC % 2 == 0 && NLOC <= 16, "rows are stored as float pairs; a row phase is at most the sixteen lanes of a DPP row (two blocks of eight columns)");
   float *L = c.L;
   const float *H = L + c.ly.H;
   const bool row = dof >= 0;
   const int B = row ? c.I(mp)[dof] : 0;
-  const int l = MAP_L(B), nI = MAP_NI(B), rowb = MAP_ROWB(B), hI = rowb - l * (l + 1) / 2;
+  const int l = MAP_L(B), nI = MAP_NI(B), rowb = MAP_ROWB(B);
   const int p0 = pos - l; // first position of the lane's island inside its group
   fs_f2 A[NLOC / 2];
   {
     // entry (l, lq) of the island's packed triangle, lq = q - p0: tri(max) + min.  Unconditional loads on an unclamped index
     // (at worst 15 words below the island's base, inside the LDS image) and a selection afterwards: behind `ok ? load : 0`
-    // every entry became an exec-masked block of ~20 instructions
+    // every entry became an exec-masked block of ~20 instructions.  Up to the diagonal (q <= pos) the entries are the lane's own
+    // row, rowb + lq = (rowb - p0) + q: one base for all of them, q in the load's offset field.  Beyond it they walk down column l,
+    // hI + tri(lq) + l, kept relative to q as well: cq(q + 1) = cq(q) + lq.
     float e[NLOC];
-    const int triL = l * (l + 1) / 2;
-    int lq = -p0, triQ = p0 * (p0 - 1) / 2; // tri(lq) for lq = -p0 (only used once lq >= l >= 0)
+    // (in bytes, so that the select is the load's address)
+    const char *Hb = (const char *)H;
+    const int rq = 4 * (rowb - p0);
+    int lq = -4 * p0, cq = 4 * (rowb - l * (l + 1) / 2 + p0 * (p0 - 1) / 2 + l);
 #pragma unroll
     for (int q = 0; q < NLOC; q++) {
-      e[q] = H[hI + (l >= lq ? triL + lq : triQ + l)];
-      lq++; triQ += lq;
+      e[q] = *(const float *)(Hb + (q <= pos ? rq : cq) + 4 * q);
+      cq += lq; lq += 4;
     }
     if (NLOC == 6)
       asm volatile("" : "+v"(e[0]), "+v"(e[1]), "+v"(e[2]), "+v"(e[3]), "+v"(e[4]), "+v"(e[5]));
@@ -955,17 +988,17 @@ template <int NLOC, class BC, class Ctx> DEV int fs_chol_phase(const Ctx &c, int
 #pragma unroll
       for (int q0 = 0; q0 < NLOC; q0 += 8)
         asm volatile("" : "+v"(e[q0]), "+v"(e[q0 + 1]), "+v"(e[q0 + 2]), "+v"(e[q0 + 3]), "+v"(e[q0 + 4]), "+v"(e[q0 + 5]), "+v"(e[q0 + 6]), "+v"(e[q0 + 7]));
-#pragma unroll
-    for (int q = 0; q < NLOC; q++) {
-      const bool ok = row && q < steps && (unsigned)(q - p0) < (unsigned)nI;
-      FS_ROW(A, q) = (!row && q == pos) ? 1.0f : (ok ? e[q] : 0.0f); // a lane without a dof: unit diagonal, zero row
-    }
+    // an entry counts if it lies inside the lane's island and below `steps`: p0 <= q < p0 + min(nI, steps - p0), one unsigned compare per entry
+    // (a lane without a dof has nI = 0: a zero row -- and a unit diagonal, at ITS position only)
+    const unsigned nq = (unsigned)max(min(nI, steps - p0), 0);
+    int diag = row ? -1 : pos;
+    asm("" : "+v"(diag)); // (one compare per entry against this register; left to itself the compiler compares with pos and ANDs each mask with !row)
+    FsRowSelect<NLOC, 0>::run(A, e, diag, p0, nq);
   }
   float b = row ? -L[c.ly.grad + dof] : 0.0f, mydinv = 0.0f, dmin = 1.0f;
-  FsCholStep<NLOC, 0, BC>::fwd(A, b, mydinv, dmin, pos, steps, bc);
-  int pos2 = pos;
-  asm volatile("" : "+v"(pos2)); // (the backward sweep derives its lane roles afresh: see FsCholStep)
-  FsCholStep<NLOC, 0, BC>::bwd(A, b, mydinv, pos2, steps, bc);
+  int posv = pos;
+  FsCholStep<NLOC, 0>::fwd(A, b, mydinv, dmin, posv, steps);
+  FsCholStep<NLOC, 0>::bwd(A, b, mydinv, posv, steps); // (derives its lane roles afresh: see FsCholStep)
   if (row) L[c.ly.p + dof] = b;
   return !(dmin > 1e-30f); // a non-positive (or NaN) pivot anywhere in this lane's group
 }
@@ -1470,9 +1503,9 @@ template <class Ctx> DEV bool fs_chol_solve(const Ctx &c, int mp, const int am =
         if (rsteps == 0) continue;
       }
       // (<= 6: what is left for the rows when the robot and the part it holds form a big island -- single parts, one per row)
-      if (rsteps <= 6) bad |= fs_chol_phase<6>(c, mp, dof, c.lane & 15, rsteps, RowBcast());
-      else if (rsteps <= 12) bad |= fs_chol_phase<12>(c, mp, dof, c.lane & 15, rsteps, RowBcast());
-      else bad |= fs_chol_phase<16>(c, mp, dof, c.lane & 15, rsteps, RowBcast());
+      if (rsteps <= 6) bad |= fs_chol_phase<6>(c, mp, dof, c.lane & 15, rsteps);
+      else if (rsteps <= 12) bad |= fs_chol_phase<12>(c, mp, dof, c.lane & 15, rsteps);
+      else bad |= fs_chol_phase<16>(c, mp, dof, c.lane & 15, rsteps);
     }
   }
   FS_CHPROF(48);
@@ -1819,9 +1852,9 @@ template <class Ctx> DEV void mw_chol_rows(const Ctx &c, int mp, const int am) {
   if (dof >= 0 && !FS_DOF_MOVES(am, dof)) { c.L[c.ly.p + dof] = 0.0f; dof = -1; } // (as in fs_chol_solve)
   rsteps = min(rsteps, (int)wave_max(dof >= 0 ? (float)((c.lane & 15) + 1) : 0.0f));
   if (rsteps == 0) return;
-  if (rsteps <= 6) bad |= fs_chol_phase<6>(c, mp, dof, c.lane & 15, rsteps, RowBcast());
-  else if (rsteps <= 12) bad |= fs_chol_phase<12>(c, mp, dof, c.lane & 15, rsteps, RowBcast());
-  else bad |= fs_chol_phase<16>(c, mp, dof, c.lane & 15, rsteps, RowBcast());
+  if (rsteps <= 6) bad |= fs_chol_phase<6>(c, mp, dof, c.lane & 15, rsteps);
+  else if (rsteps <= 12) bad |= fs_chol_phase<12>(c, mp, dof, c.lane & 15, rsteps);
+  else bad |= fs_chol_phase<16>(c, mp, dof, c.lane & 15, rsteps);
   if (__ballot(bad != 0) && c.lane == 0) c.I(c.ly.mwc)[MWC_BAD] = 1;
 }
 template <class Ctx> DEV int mw_chol_big(const Ctx &c, int mp, const int am, const int asm_ok) {

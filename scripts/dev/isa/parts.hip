@@ -5,8 +5,8 @@
 typedef SpecCtx<Spec_sawyer_table_lack_0825> C;
 #define K(name, ...) extern "C" __global__ __launch_bounds__(64) void name(const DModel *mp, int a, int b, float *out) { \
   extern __shared__ float lds[]; CModel &m = *(CModel *)mp; C c(lds, m, (int)threadIdx.x, 100, 1e-8f); __VA_ARGS__ }
-K(isa_chol12, { out[c.lane] = fs_chol_phase<12>(c, c.ly.hmap, a + c.lane < 39 ? c.lane : -1, c.lane & 15, b, RowBcast()); })
-K(isa_chol16, { out[c.lane] = fs_chol_phase<16>(c, c.ly.hmap, a + c.lane < 39 ? c.lane : -1, c.lane & 15, b, RowBcast()); })
+K(isa_chol12, { out[c.lane] = fs_chol_phase<12>(c, c.ly.hmap, a + c.lane < 39 ? c.lane : -1, c.lane & 15, b); })
+K(isa_chol16, { out[c.lane] = fs_chol_phase<16>(c, c.ly.hmap, a + c.lane < 39 ? c.lane : -1, c.lane & 15, b); })
 K(isa_cholsolve, { out[c.lane] = fs_chol_solve(c, c.ly.hmap); })
 K(isa_grad, { SolSlot S = fs_load_slots(c); SlotK sk = fs_gradient(c, S); out[c.lane] = sk.K[0] + sk.K[1] + sk.K[2] + sk.K[3] + sk.K[4] + sk.K[5] + sk.zone + sk.on; })
 K(isa_hess, { SolSlot S = fs_load_slots(c); SlotK sk; sk.on = a > c.lane; sk.zone = b; for (int q = 0; q < 6; q++) sk.K[q] = out[64 * q + c.lane]; fs_hessian(c, sk, S); })
