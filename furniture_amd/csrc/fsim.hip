@@ -514,6 +514,7 @@ struct RayState; // fsim_rays.hpp
 struct ProbeState; // fsim_probes.hpp
 struct PairState; // fsim_pairs.hpp
 struct FrameState; // fsim_frames.hpp
+struct DynState; // fsim_dynamics.hpp
 struct KernelSet { const char *name; PhysicsFn physics; EnvStepFn env_step; PhysicsFn physics_mw; EnvStepFn env_step_mw; EnvStepXFn env_step_x; };
 enum { MW_OFF = 0, MW_RULE = 1, MW_ALL = 2 }; // fsim::mw_mode
 
@@ -600,6 +601,7 @@ struct fsim {
   ProbeState *probe = nullptr; // distance probes: tables and pose scratch (fsim_set_probes): nothing is allocated or launched without them
   PairState *pair = nullptr; // geom-pair distance sensors: tables and pose scratch (fsim_set_pairs): nothing is allocated or launched without them
   FrameState *frame = nullptr; // body / site frame sensors: the frame table (fsim_set_frames): nothing is allocated or launched without it
+  DynState *dyn = nullptr; // mass matrix, inverse inertia and bias forces: the dof selection (fsim_set_dynamics): nothing is allocated or launched without it
 };
 
 static void la_policy(fsim *s);
@@ -1019,6 +1021,7 @@ static void ray_free(fsim *s);
 static void probe_free(fsim *s);
 static void pair_free(fsim *s);
 static void frame_free(fsim *s);
+static void dyn_free(fsim *s);
 extern "C" void fsim_destroy(fsim_t *s) {
   if (!s) return;
   hipSetDevice(s->device);
@@ -1032,6 +1035,7 @@ extern "C" void fsim_destroy(fsim_t *s) {
   probe_free(s);
   pair_free(s);
   frame_free(s);
+  dyn_free(s);
   hipFree(s->d_sh_state); hipFree(s->d_sh_obs); hipFree(s->d_sh_prog); hipFree(s->d_sh_serial); hipFree(s->d_tab_serial); hipFree(s->d_sh_jobs);
   if (s->xfer) { hipStreamSynchronize(s->xfer); hipStreamDestroy(s->xfer); }
   hipFree(s->d_ly_r[0]); hipFree(s->d_ly_r[1]); hipFree(s->d_ly_r[2]); hipFree(s->d_prev); hipFree(s->d_ovf_list); hipFree(s->d_ovf_list2);
@@ -1689,3 +1693,4 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
 #include "fsim_probes.hpp"
 #include "fsim_pairs.hpp"
 #include "fsim_frames.hpp"
+#include "fsim_dynamics.hpp"

@@ -364,9 +364,10 @@ class FurnitureBatchEnv:
     probes = None
     pairs = None
     frames = None
+    dynamics = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -409,7 +410,11 @@ class FurnitureBatchEnv:
         frames: a furniture_amd.frames.FrameSet (needs none of the others) -- the observations then also hold frame_pos (float32
         [n, S, 3], each sensor's frame origin in its reference frame, metres), frame_quat (float32 [n, S, 4], wxyz, its orientation in the
         reference frame) and, with velocity=True / jacobian=True, frame_vel (float32 [n, S, 6], the rate of frame_pos and the relative
-        angular velocity) and frame_jac (float32 [n, S, 6, nv], frame_vel = frame_jac @ qvel), from one fsim_frame_state call."""
+        angular velocity) and frame_jac (float32 [n, S, 6, nv], frame_vel = frame_jac @ qvel), from one fsim_frame_state call.
+        dynamics: a furniture_amd.dynamics.Dynamics (needs none of the others) -- the observations then also hold those it asks for of
+        dyn_mass (float32 [n, K, K], the joint-space inertia restricted to its K dofs), dyn_minv (float32 [n, K, K], the inverse of the
+        whole inertia restricted to them), dyn_bias (float32 [n, K], qfrc_bias) and dyn_gravity (float32 [n, K], the same at qvel = 0),
+        from one fsim_dynamics call."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -434,6 +439,9 @@ class FurnitureBatchEnv:
         if frames is not None:
             from .frames import check as check_frames
             check_frames(frames)
+        if dynamics is not None:
+            from .dynamics import check as check_dynamics
+            check_dynamics(dynamics)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -566,6 +574,10 @@ class FurnitureBatchEnv:
         if frames is not None:  # (without frames: no allocation, no launch, the same observation dict)
             self.sim.set_frames(frames)
             self._frame_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.frame_shapes().items()}
+        self.dynamics = dynamics
+        if dynamics is not None:  # (without dynamics: no allocation, no launch, the same observation dict)
+            self.sim.set_dynamics(dynamics)
+            self._dyn_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.dynamics_shapes().items()}
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -639,6 +651,9 @@ class FurnitureBatchEnv:
                 sp.append(("frame_vel", spaces.Box(-np.inf, np.inf, shape=(r, 6), dtype=np.float32)))
             if self.frames.jacobian:
                 sp.append(("frame_jac", spaces.Box(-np.inf, np.inf, shape=(r, 6, self.model.nv), dtype=np.float32)))
+        if self.dynamics is not None:
+            for k, (sh, _) in self.sim.dynamics_shapes().items():
+                sp.append((k, spaces.Box(-np.inf, np.inf, shape=sh, dtype=np.float32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -655,7 +670,8 @@ class FurnitureBatchEnv:
         the flow / velocity images when they are set (from one fsim_render_flow call, last: again one more ray pass when there are any) and
         the ray sensors' outputs when a ray set is given (from one fsim_cast_rays call) and the distance probes' outputs when a probe set
         is given (from one fsim_probe_distance call) and the pair sensors' outputs when a pair set is given (from one fsim_pair_distance
-        call) and the frame sensors' outputs when a frame set is given (from one fsim_frame_state call)"""
+        call) and the frame sensors' outputs when a frame set is given (from one fsim_frame_state call) and the dynamics tensors when a
+        Dynamics is given (from one fsim_dynamics call)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -689,6 +705,8 @@ class FurnitureBatchEnv:
             out.update(self.sim.pair_distance(out=self._pair_out))
         if self.frames is not None:  # one fsim_frame_state call; independent of all the others
             out.update(self.sim.frame_state(out=self._frame_out))
+        if self.dynamics is not None:  # one fsim_dynamics call; independent of all the others
+            out.update(self.sim.dynamics(out=self._dyn_out))
         return out
 
     def _at_points(self, image):
@@ -1034,7 +1052,7 @@ class _SingleEnv:
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
                                          point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays,
-                                         probes=old.probes, pairs=old.pairs, frames=old.frames)
+                                         probes=old.probes, pairs=old.pairs, frames=old.frames, dynamics=old.dynamics)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

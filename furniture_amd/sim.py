@@ -89,7 +89,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -203,6 +203,8 @@ def lib():
         L.fsim_pair_distance.argtypes = [ctypes.c_void_p] * 5
         L.fsim_set_frames.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.fsim_frame_state.argtypes = [ctypes.c_void_p] * 5
+        L.fsim_set_dynamics.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.fsim_dynamics.argtypes = [ctypes.c_void_p] * 5
         _LIB = L
     return _LIB
 
@@ -234,6 +236,8 @@ PROBE_SYMBOLS = ["fsim_set_probes", "fsim_probe_distance"]
 PAIR_SYMBOLS = ["fsim_set_pairs", "fsim_pair_distance"]
 # the frame-sensor entry points: a header of their own (include/fsim_frames.h), exported by the same library
 FRAME_SYMBOLS = ["fsim_set_frames", "fsim_frame_state"]
+# the dynamics-tensor entry points: a header of their own (include/fsim_dynamics.h), exported by the same library
+DYN_SYMBOLS = ["fsim_set_dynamics", "fsim_dynamics"]
 
 
 def preassembled_rows(model, preassembled):
@@ -921,6 +925,59 @@ class FSim:
         cur = torch.cuda.current_stream(self.device)
         self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
         self._chk(lib().fsim_frame_state(self._h, *[res[k].data_ptr() if k in res else None for k in ("frame_pos", "frame_quat", "frame_vel", "frame_jac")]))
+        cur.wait_stream(self.torch_stream)
+        return res
+
+    # -- mass-matrix, inverse-inertia and bias-force tensors (include/fsim_dynamics.h, furniture_amd/dynamics.py) -------------------------
+    dyn = None
+
+    def set_dynamics(self, spec):
+        """Replace the handle's dynamics selection (a furniture_amd.dynamics.Dynamics; None clears it); checked on the host first, then
+        by the library.  Independent of the cameras, the rays, the probes, the pairs and the frames: needs and disturbs none of them."""
+        from .dynamics import Dynamics, dof_table
+        if spec is None:
+            self._chk(lib().fsim_set_dynamics(self._h, 0, None))
+            self.dyn = None
+            return
+        if not isinstance(spec, Dynamics):
+            raise TypeError("set_dynamics: a furniture_amd.dynamics.Dynamics, not %r" % type(spec).__name__)
+        tab = dof_table(self.cm, spec)
+        self._chk(lib().fsim_set_dynamics(self._h, len(tab), tab.ctypes.data))
+        self.dyn = spec
+        self._dyn_k = len(tab)
+
+    def dynamics_shapes(self):
+        """{key: (shape, dtype)} of dynamics' outputs (without the n_envs dimension)"""
+        torch = self.torch
+        if self.dyn is None:
+            raise FsimError("dynamics_shapes: no dof selection (FSim.set_dynamics)")
+        k = self._dyn_k
+        shapes = dict(dyn_mass=(k, k), dyn_minv=(k, k), dyn_bias=(k,), dyn_gravity=(k,))
+        return {key: (shapes[key], torch.float32) for key in self.dyn.keys()}
+
+    def dynamics(self, out=None):
+        """The dynamics tensors of every env (include/fsim_dynamics.h), for the state sync() leaves -> dict of device tensors, those the
+        Dynamics asks for: dyn_mass (float32 [n, K, K], M[dofs][:, dofs]), dyn_minv (float32 [n, K, K], the inverse of the whole M
+        restricted to dofs), dyn_bias (float32 [n, K], qfrc_bias[dofs]) and dyn_gravity (float32 [n, K], the same at qvel = 0).  out: a
+        dict of such tensors to write into instead of new ones; a key that is there alone is computed alone.  Ordered with torch's
+        current stream both ways."""
+        torch = self.torch
+        if self.dyn is None:
+            raise FsimError("dynamics: no dof selection (FSim.set_dynamics)")
+        want = self.dynamics_shapes()
+        if out is not None:
+            if not out or any(k not in want for k in out):
+                raise ValueError("dynamics: out holds %s (of %s)" % (sorted(out), sorted(want)))
+            want = {k: want[k] for k in want if k in out}
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
+                raise ValueError("dynamics: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
+            res[k] = t
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_dynamics(self._h, *[res[k].data_ptr() if k in res else None for k in ("dyn_mass", "dyn_minv", "dyn_bias", "dyn_gravity")]))
         cur.wait_stream(self.torch_stream)
         return res
 

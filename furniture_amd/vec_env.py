@@ -69,6 +69,9 @@ class FurnitureVecEnv:
         if kw.pop("frames", None) is not None:
             raise NotImplementedError("frames= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., frames=FrameSet(...)), whose frame outputs stay on the device")
+        if kw.pop("dynamics", None) is not None:
+            raise NotImplementedError("dynamics= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., dynamics=Dynamics(...)), whose dynamics outputs stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
