@@ -365,9 +365,10 @@ class FurnitureBatchEnv:
     pairs = None
     frames = None
     dynamics = None
+    contacts = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, contacts=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -414,7 +415,12 @@ class FurnitureBatchEnv:
         dynamics: a furniture_amd.dynamics.Dynamics (needs none of the others) -- the observations then also hold those it asks for of
         dyn_mass (float32 [n, K, K], the joint-space inertia restricted to its K dofs), dyn_minv (float32 [n, K, K], the inverse of the
         whole inertia restricted to them), dyn_bias (float32 [n, K], qfrc_bias) and dyn_gravity (float32 [n, K], the same at qvel = 0),
-        from one fsim_dynamics call."""
+        from one fsim_dynamics call.
+        contacts: a furniture_amd.contacts.ContactSet (needs none of the others) -- the observations then also hold contact_force (float32
+        [n, S, 3], the net world-frame force side b of each sensor exerts on its side a, at the state the observation describes),
+        contact_touch (float32 [n, S], the sum of the normal forces), contact_count (int32 [n, S], listed contacts), contact_status (int32
+        [n], bit 0: contacts were dropped, bit 1: the solve is not to be trusted) and, with contacts=True in the set, the contact list
+        con_geoms / con_pos / con_normal / con_dist / con_force / con_fn, from one fsim_contact_forces call."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -442,6 +448,9 @@ class FurnitureBatchEnv:
         if dynamics is not None:
             from .dynamics import check as check_dynamics
             check_dynamics(dynamics)
+        if contacts is not None:
+            from .contacts import check as check_contacts
+            check_contacts(contacts)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -578,6 +587,10 @@ class FurnitureBatchEnv:
         if dynamics is not None:  # (without dynamics: no allocation, no launch, the same observation dict)
             self.sim.set_dynamics(dynamics)
             self._dyn_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.dynamics_shapes().items()}
+        self.contacts = contacts
+        if contacts is not None:  # (without contacts: no allocation, no launch, the same observation dict)
+            self.sim.set_contacts(contacts)
+            self._con_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.contact_shapes().items()}
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -654,6 +667,13 @@ class FurnitureBatchEnv:
         if self.dynamics is not None:
             for k, (sh, _) in self.sim.dynamics_shapes().items():
                 sp.append((k, spaces.Box(-np.inf, np.inf, shape=sh, dtype=np.float32)))
+        if self.contacts is not None:
+            for k, (sh, dt) in self.sim.contact_shapes().items():
+                if dt == self.sim.torch.float32:
+                    sp.append((k, spaces.Box(0.0 if k in ("contact_touch", "con_fn") else -np.inf, np.inf, shape=sh, dtype=np.float32)))
+                else:  # contact_count, contact_status, con_geoms
+                    lo, hi = {"contact_count": (0, self.sim.max_contacts), "contact_status": (0, 3), "con_geoms": (-1, self.model.ngeom - 1)}[k]
+                    sp.append((k, spaces.Box(lo, hi, shape=sh, dtype=np.int32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -671,7 +691,8 @@ class FurnitureBatchEnv:
         the ray sensors' outputs when a ray set is given (from one fsim_cast_rays call) and the distance probes' outputs when a probe set
         is given (from one fsim_probe_distance call) and the pair sensors' outputs when a pair set is given (from one fsim_pair_distance
         call) and the frame sensors' outputs when a frame set is given (from one fsim_frame_state call) and the dynamics tensors when a
-        Dynamics is given (from one fsim_dynamics call)"""
+        Dynamics is given (from one fsim_dynamics call) and the contact sensors' outputs when a contact set is given (from one
+        fsim_contact_forces call)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -707,6 +728,8 @@ class FurnitureBatchEnv:
             out.update(self.sim.frame_state(out=self._frame_out))
         if self.dynamics is not None:  # one fsim_dynamics call; independent of all the others
             out.update(self.sim.dynamics(out=self._dyn_out))
+        if self.contacts is not None:  # one fsim_contact_forces call; independent of all the others, reads the records only
+            out.update(self.sim.contact_forces(out=self._con_out))
         return out
 
     def _at_points(self, image):
@@ -1052,7 +1075,7 @@ class _SingleEnv:
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
                                          point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays,
-                                         probes=old.probes, pairs=old.pairs, frames=old.frames, dynamics=old.dynamics)
+                                         probes=old.probes, pairs=old.pairs, frames=old.frames, dynamics=old.dynamics, contacts=old.contacts)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

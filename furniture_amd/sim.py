@@ -82,6 +82,19 @@ class FsimFrameSensor(ctypes.Structure):
     _fields_ = [("frame", FsimFrame), ("ref", FsimFrame)]
 
 
+class FsimContactSensor(ctypes.Structure):
+    """fsim_contact_sensor_t (include/fsim_contacts.h)"""
+    _fields_ = [("a", ctypes.POINTER(ctypes.c_int32)), ("b", ctypes.POINTER(ctypes.c_int32)), ("na", ctypes.c_int32), ("nb", ctypes.c_int32)]
+
+
+CONTACT_OUT_FIELDS = ("force", "touch", "count", "status", "con_geoms", "con_pos", "con_normal", "con_dist", "con_force", "con_fn")
+
+
+class FsimContactOut(ctypes.Structure):
+    """fsim_contact_out_t (include/fsim_contacts.h): device pointers, None = not asked for"""
+    _fields_ = [(k, ctypes.c_void_p) for k in CONTACT_OUT_FIELDS]
+
+
 def library_path():
     return _LIBPATH
 
@@ -89,7 +102,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h", "fsim_contacts.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -205,6 +218,8 @@ def lib():
         L.fsim_frame_state.argtypes = [ctypes.c_void_p] * 5
         L.fsim_set_dynamics.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.fsim_dynamics.argtypes = [ctypes.c_void_p] * 5
+        L.fsim_set_contacts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.fsim_contact_forces.argtypes = [ctypes.c_void_p, ctypes.POINTER(FsimContactOut)]
         _LIB = L
     return _LIB
 
@@ -238,6 +253,8 @@ PAIR_SYMBOLS = ["fsim_set_pairs", "fsim_pair_distance"]
 FRAME_SYMBOLS = ["fsim_set_frames", "fsim_frame_state"]
 # the dynamics-tensor entry points: a header of their own (include/fsim_dynamics.h), exported by the same library
 DYN_SYMBOLS = ["fsim_set_dynamics", "fsim_dynamics"]
+# the contact-force entry points: a header of their own (include/fsim_contacts.h), exported by the same library
+CONTACT_SYMBOLS = ["fsim_set_contacts", "fsim_contact_forces"]
 
 
 def preassembled_rows(model, preassembled):
@@ -978,6 +995,66 @@ class FSim:
         cur = torch.cuda.current_stream(self.device)
         self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
         self._chk(lib().fsim_dynamics(self._h, *[res[k].data_ptr() if k in res else None for k in ("dyn_mass", "dyn_minv", "dyn_bias", "dyn_gravity")]))
+        cur.wait_stream(self.torch_stream)
+        return res
+
+    # -- contact-force and touch sensors (include/fsim_contacts.h, furniture_amd/contacts.py) -------------------------------------------
+    contacts = None
+
+    def set_contacts(self, contact_set):
+        """Replace the handle's contact sensors (a furniture_amd.contacts.ContactSet; None clears them); checked on the host first, then
+        by the library.  Independent of the cameras, the rays, the probes, the pairs, the frames and the dynamics tensors."""
+        from .contacts import MAX_SLOTS, ContactSet, sensor_table
+        if contact_set is None:
+            self._chk(lib().fsim_set_contacts(self._h, 0, None))
+            self.contacts = None
+            return
+        if not isinstance(contact_set, ContactSet):
+            raise TypeError("set_contacts: a furniture_amd.contacts.ContactSet, not %r" % type(contact_set).__name__)
+        if self.max_contacts > MAX_SLOTS:
+            raise ValueError("contacts: the handle has %d contact slots (the contact-force pass serves at most %d)" % (self.max_contacts, MAX_SLOTS))
+        tab = sensor_table(self.cm, contact_set)
+        self._chk(lib().fsim_set_contacts(self._h, len(tab), ctypes.cast(tab, ctypes.c_void_p)))
+        self.contacts = contact_set
+
+    def contact_shapes(self):
+        """{key: (shape, dtype)} of contact_forces' outputs (without the n_envs dimension)"""
+        torch = self.torch
+        if self.contacts is None:
+            raise FsimError("contact_shapes: no sensor set (FSim.set_contacts)")
+        s, c, f, i = self.contacts.n_sensors, self.max_contacts, torch.float32, torch.int32
+        shapes = dict(contact_force=((s, 3), f), contact_touch=((s,), f), contact_count=((s,), i), contact_status=((), i),
+                      con_geoms=((c, 2), i), con_pos=((c, 3), f), con_normal=((c, 3), f), con_dist=((c,), f), con_force=((c, 3), f), con_fn=((c,), f))
+        return {key: shapes[key] for key in self.contacts.keys()}
+
+    def contact_forces(self, out=None):
+        """The contact forces of every env (include/fsim_contacts.h), for the state sync() leaves -> dict of device tensors:
+        contact_force (float32 [n, S, 3], the net world force side b exerts on side a), contact_touch (float32 [n, S], the sum of the
+        normal forces), contact_count (int32 [n, S], listed contacts), contact_status (int32 [n], bit 0 contacts dropped, bit 1 solve not
+        to be trusted) and, with the set's contacts=True, con_geoms (int32 [n, C, 2]), con_pos, con_normal, con_force (float32 [n, C, 3]),
+        con_dist and con_fn (float32 [n, C]).  out: a dict of such tensors to write into instead of new ones; a key that is there alone
+        is computed alone.  Reads the env records and writes nothing else.  Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if self.contacts is None:
+            raise FsimError("contact_forces: no sensor set (FSim.set_contacts)")
+        want = self.contact_shapes()
+        if out is not None:
+            if not out or any(k not in want for k in out):
+                raise ValueError("contact_forces: out holds %s (of %s)" % (sorted(out), sorted(want)))
+            want = {k: want[k] for k in want if k in out}
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
+                raise ValueError("contact_forces: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
+            res[k] = t
+        ptrs = FsimContactOut()
+        for field in CONTACT_OUT_FIELDS:
+            key = field if field.startswith("con_") else "contact_" + field
+            setattr(ptrs, field, res[key].data_ptr() if key in res else None)
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_contact_forces(self._h, ctypes.byref(ptrs)))
         cur.wait_stream(self.torch_stream)
         return res
 
