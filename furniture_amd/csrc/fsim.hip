@@ -516,6 +516,7 @@ struct PairState; // fsim_pairs.hpp
 struct FrameState; // fsim_frames.hpp
 struct DynState; // fsim_dynamics.hpp
 struct ConState; // fsim_contacts.hpp
+struct WrState; // fsim_wrench.hpp
 struct KernelSet { const char *name; PhysicsFn physics; EnvStepFn env_step; PhysicsFn physics_mw; EnvStepFn env_step_mw; EnvStepXFn env_step_x; };
 enum { MW_OFF = 0, MW_RULE = 1, MW_ALL = 2 }; // fsim::mw_mode
 
@@ -604,6 +605,7 @@ struct fsim {
   FrameState *frame = nullptr; // body / site frame sensors: the frame table (fsim_set_frames): nothing is allocated or launched without it
   DynState *dyn = nullptr; // mass matrix, inverse inertia and bias forces: the dof selection (fsim_set_dynamics): nothing is allocated or launched without it
   ConState *con = nullptr; // contact-force and touch sensors: the sensor table (fsim_set_contacts): nothing is allocated or launched without it
+  WrState *wr = nullptr; // force-torque, accelerometer and joint-load sensors: the sensor table (fsim_set_wrenches): nothing is allocated or launched without it
 };
 
 static void la_policy(fsim *s);
@@ -1025,6 +1027,7 @@ static void pair_free(fsim *s);
 static void frame_free(fsim *s);
 static void dyn_free(fsim *s);
 static void con_free(fsim *s);
+static void wr_free(fsim *s);
 extern "C" void fsim_destroy(fsim_t *s) {
   if (!s) return;
   hipSetDevice(s->device);
@@ -1040,6 +1043,7 @@ extern "C" void fsim_destroy(fsim_t *s) {
   frame_free(s);
   dyn_free(s);
   con_free(s);
+  wr_free(s);
   hipFree(s->d_sh_state); hipFree(s->d_sh_obs); hipFree(s->d_sh_prog); hipFree(s->d_sh_serial); hipFree(s->d_tab_serial); hipFree(s->d_sh_jobs);
   if (s->xfer) { hipStreamSynchronize(s->xfer); hipStreamDestroy(s->xfer); }
   hipFree(s->d_ly_r[0]); hipFree(s->d_ly_r[1]); hipFree(s->d_ly_r[2]); hipFree(s->d_prev); hipFree(s->d_ovf_list); hipFree(s->d_ovf_list2);
@@ -1699,3 +1703,4 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
 #include "fsim_frames.hpp"
 #include "fsim_dynamics.hpp"
 #include "fsim_contacts.hpp"
+#include "fsim_wrench.hpp"

@@ -99,6 +99,8 @@ def step_wait_and_gather(sim, obs, reward, done, tag=0, stream=None, group=None)
         raise NotImplementedError("step_wait_and_gather: dynamics tensors are not part of the multi-GPU gather; compute them on each rank instead")
     if getattr(sim, "contacts", None) is not None:
         raise NotImplementedError("step_wait_and_gather: contact-force outputs are not part of the multi-GPU gather; compute them on each rank instead")
+    if getattr(sim, "wrench_set", None) is not None:
+        raise NotImplementedError("step_wait_and_gather: wrench-sensor outputs are not part of the multi-GPU gather; compute them on each rank instead")
     sim.sync()
     out = gather_observations(obs, reward, done, tag=tag, stream=stream, group=group)
     if stream is not None and obs.is_cuda:

@@ -366,9 +366,10 @@ class FurnitureBatchEnv:
     frames = None
     dynamics = None
     contacts = None
+    wrenches = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, contacts=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, contacts=None, wrenches=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -420,7 +421,14 @@ class FurnitureBatchEnv:
         [n, S, 3], the net world-frame force side b of each sensor exerts on its side a, at the state the observation describes),
         contact_touch (float32 [n, S], the sum of the normal forces), contact_count (int32 [n, S], listed contacts), contact_status (int32
         [n], bit 0: contacts were dropped, bit 1: the solve is not to be trusted) and, with contacts=True in the set, the contact list
-        con_geoms / con_pos / con_normal / con_dist / con_force / con_fn, from one fsim_contact_forces call."""
+        con_geoms / con_pos / con_normal / con_dist / con_force / con_fn, from one fsim_contact_forces call.
+        wrenches: a furniture_amd.wrench.WrenchSet (needs none of the others) -- the observations then also hold wrench_force and
+        wrench_torque (float32 [n, S, 3]: what the parent side exerts on each sensor body's subtree through the body's joint, the torque
+        about the sensor origin, in the sensor frame, at the state the observation describes), wrench_accel (float32 [n, S, 3], the
+        accelerometer: +9.81 along world z at rest), wrench_angacc (float32 [n, S, 3]), wrench_status (int32 [n], the bits of
+        contact_status) and, with external=True / joint=True in the set, wrench_external (float32 [n, S, 6], the net world-frame force and
+        torque of contacts, welds and applied forces on the sensor's body) and wrench_qacc / wrench_qfrc_constraint (float32 [n, nv]),
+        from one fsim_wrenches call."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -451,6 +459,9 @@ class FurnitureBatchEnv:
         if contacts is not None:
             from .contacts import check as check_contacts
             check_contacts(contacts)
+        if wrenches is not None:
+            from .wrench import check as check_wrenches
+            check_wrenches(wrenches)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -591,6 +602,10 @@ class FurnitureBatchEnv:
         if contacts is not None:  # (without contacts: no allocation, no launch, the same observation dict)
             self.sim.set_contacts(contacts)
             self._con_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.contact_shapes().items()}
+        self.wrenches = wrenches
+        if wrenches is not None:  # (without wrenches: no allocation, no launch, the same observation dict)
+            self.sim.set_wrenches(wrenches)
+            self._wr_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.wrench_shapes().items()}
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -674,6 +689,12 @@ class FurnitureBatchEnv:
                 else:  # contact_count, contact_status, con_geoms
                     lo, hi = {"contact_count": (0, self.sim.max_contacts), "contact_status": (0, 3), "con_geoms": (-1, self.model.ngeom - 1)}[k]
                     sp.append((k, spaces.Box(lo, hi, shape=sh, dtype=np.int32)))
+        if self.wrenches is not None:
+            for k, (sh, dt) in self.sim.wrench_shapes().items():
+                if dt == self.sim.torch.float32:
+                    sp.append((k, spaces.Box(-np.inf, np.inf, shape=sh, dtype=np.float32)))
+                else:  # wrench_status
+                    sp.append((k, spaces.Box(0, 3, shape=sh, dtype=np.int32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -692,7 +713,7 @@ class FurnitureBatchEnv:
         is given (from one fsim_probe_distance call) and the pair sensors' outputs when a pair set is given (from one fsim_pair_distance
         call) and the frame sensors' outputs when a frame set is given (from one fsim_frame_state call) and the dynamics tensors when a
         Dynamics is given (from one fsim_dynamics call) and the contact sensors' outputs when a contact set is given (from one
-        fsim_contact_forces call)"""
+        fsim_contact_forces call) and the wrench sensors' outputs when a wrench set is given (from one fsim_wrenches call)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -730,6 +751,8 @@ class FurnitureBatchEnv:
             out.update(self.sim.dynamics(out=self._dyn_out))
         if self.contacts is not None:  # one fsim_contact_forces call; independent of all the others, reads the records only
             out.update(self.sim.contact_forces(out=self._con_out))
+        if self.wrenches is not None:  # one fsim_wrenches call; independent of all the others, reads the records only
+            out.update(self.sim.wrenches(out=self._wr_out))
         return out
 
     def _at_points(self, image):
@@ -1075,7 +1098,7 @@ class _SingleEnv:
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
                                          point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays,
-                                         probes=old.probes, pairs=old.pairs, frames=old.frames, dynamics=old.dynamics, contacts=old.contacts)
+                                         probes=old.probes, pairs=old.pairs, frames=old.frames, dynamics=old.dynamics, contacts=old.contacts, wrenches=old.wrenches)
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

@@ -71,6 +71,9 @@ class FurnitureMixedBatchEnv:
         if kw.pop("contacts", None) is not None:
             raise NotImplementedError("contacts= is not supported by the mixed-furniture batch (one contact set per FurnitureBatchEnv): "
                                       "make one FurnitureBatchEnv per furniture instead")
+        if kw.pop("wrenches", None) is not None:
+            raise NotImplementedError("wrenches= is not supported by the mixed-furniture batch (one wrench set per FurnitureBatchEnv): "
+                                      "make one FurnitureBatchEnv per furniture instead")
         cfg = config if config is not None else make_config()
         for key, v in kw.items():
             setattr(cfg, key, v)

@@ -95,6 +95,19 @@ class FsimContactOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in CONTACT_OUT_FIELDS]
 
 
+class FsimWrenchSensor(ctypes.Structure):
+    """fsim_wrench_sensor_t (include/fsim_wrench.h)"""
+    _fields_ = [("body", ctypes.c_int32), ("pos", ctypes.c_float * 3), ("quat", ctypes.c_float * 4)]
+
+
+WRENCH_OUT_FIELDS = ("force", "torque", "accel", "angacc", "external", "qacc", "qfrc_constraint", "status")
+
+
+class FsimWrenchOut(ctypes.Structure):
+    """fsim_wrench_out_t (include/fsim_wrench.h): device pointers, None = not asked for"""
+    _fields_ = [(k, ctypes.c_void_p) for k in WRENCH_OUT_FIELDS]
+
+
 def library_path():
     return _LIBPATH
 
@@ -102,7 +115,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h", "fsim_contacts.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h", "fsim_contacts.h", "fsim_wrench.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -220,6 +233,8 @@ def lib():
         L.fsim_dynamics.argtypes = [ctypes.c_void_p] * 5
         L.fsim_set_contacts.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.fsim_contact_forces.argtypes = [ctypes.c_void_p, ctypes.POINTER(FsimContactOut)]
+        L.fsim_set_wrenches.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.fsim_wrenches.argtypes = [ctypes.c_void_p, ctypes.POINTER(FsimWrenchOut)]
         _LIB = L
     return _LIB
 
@@ -255,6 +270,8 @@ FRAME_SYMBOLS = ["fsim_set_frames", "fsim_frame_state"]
 DYN_SYMBOLS = ["fsim_set_dynamics", "fsim_dynamics"]
 # the contact-force entry points: a header of their own (include/fsim_contacts.h), exported by the same library
 CONTACT_SYMBOLS = ["fsim_set_contacts", "fsim_contact_forces"]
+# the wrench-sensor entry points: a header of their own (include/fsim_wrench.h), exported by the same library
+WRENCH_SYMBOLS = ["fsim_set_wrenches", "fsim_wrenches"]
 
 
 def preassembled_rows(model, preassembled):
@@ -1055,6 +1072,64 @@ class FSim:
         cur = torch.cuda.current_stream(self.device)
         self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
         self._chk(lib().fsim_contact_forces(self._h, ctypes.byref(ptrs)))
+        cur.wait_stream(self.torch_stream)
+        return res
+
+    # -- force-torque, accelerometer and joint-load sensors (include/fsim_wrench.h, furniture_amd/wrench.py) ------------------------------
+    wrench_set = None
+
+    def set_wrenches(self, wrench_set):
+        """Replace the handle's wrench sensors (a furniture_amd.wrench.WrenchSet; None clears them); checked on the host first, then by the
+        library.  Independent of every other sensor family."""
+        from .wrench import MAX_SLOTS, WrenchSet, sensor_table
+        if wrench_set is None:
+            self._chk(lib().fsim_set_wrenches(self._h, 0, None))
+            self.wrench_set = None
+            return
+        if not isinstance(wrench_set, WrenchSet):
+            raise TypeError("set_wrenches: a furniture_amd.wrench.WrenchSet, not %r" % type(wrench_set).__name__)
+        if self.max_contacts > MAX_SLOTS:
+            raise ValueError("wrenches: the handle has %d contact slots (the wrench pass serves at most %d)" % (self.max_contacts, MAX_SLOTS))
+        tab = sensor_table(self.cm, wrench_set)
+        self._chk(lib().fsim_set_wrenches(self._h, len(tab), ctypes.cast(tab, ctypes.c_void_p)))
+        self.wrench_set = wrench_set
+
+    def wrench_shapes(self):
+        """{key: (shape, dtype)} of wrenches' outputs (without the n_envs dimension)"""
+        torch = self.torch
+        if self.wrench_set is None:
+            raise FsimError("wrench_shapes: no sensor set (FSim.set_wrenches)")
+        s, f, i = self.wrench_set.n_sensors, torch.float32, torch.int32
+        shapes = dict(wrench_force=((s, 3), f), wrench_torque=((s, 3), f), wrench_accel=((s, 3), f), wrench_angacc=((s, 3), f),
+                      wrench_external=((s, 6), f), wrench_qacc=((self.nv,), f), wrench_qfrc_constraint=((self.nv,), f), wrench_status=((), i))
+        return {key: shapes[key] for key in self.wrench_set.keys()}
+
+    def wrenches(self, out=None):
+        """The wrench sensors of every env (include/fsim_wrench.h), for the state sync() leaves -> dict of device tensors: wrench_force,
+        wrench_torque, wrench_accel, wrench_angacc (float32 [n, S, 3], sensor frame), wrench_status (int32 [n]) and, with the set's
+        external=True, wrench_external (float32 [n, S, 6], world frame), with joint=True wrench_qacc and wrench_qfrc_constraint (float32
+        [n, nv]).  out: a dict of such tensors to write into instead of new ones; a key that is there alone is computed alone.  Reads the
+        env records and writes nothing else.  Ordered with torch's current stream both ways."""
+        torch = self.torch
+        if self.wrench_set is None:
+            raise FsimError("wrenches: no sensor set (FSim.set_wrenches)")
+        want = self.wrench_shapes()
+        if out is not None:
+            if not out or any(k not in want for k in out):
+                raise ValueError("wrenches: out holds %s (of %s)" % (sorted(out), sorted(want)))
+            want = {k: want[k] for k in want if k in out}
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
+                raise ValueError("wrenches: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
+            res[k] = t
+        ptrs = FsimWrenchOut()
+        for field in WRENCH_OUT_FIELDS:
+            setattr(ptrs, field, res["wrench_" + field].data_ptr() if "wrench_" + field in res else None)
+        cur = torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(lib().fsim_wrenches(self._h, ctypes.byref(ptrs)))
         cur.wait_stream(self.torch_stream)
         return res
 

@@ -75,6 +75,9 @@ class FurnitureVecEnv:
         if kw.pop("contacts", None) is not None:
             raise NotImplementedError("contacts= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., contacts=ContactSet(...)), whose contact outputs stay on the device")
+        if kw.pop("wrenches", None) is not None:
+            raise NotImplementedError("wrenches= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., wrenches=WrenchSet(...)), whose wrench outputs stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
