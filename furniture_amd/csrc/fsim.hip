@@ -1016,45 +1016,6 @@ extern "C" int fsim_create(const void *model_blob, size_t nbytes, int n_envs, in
   return FSIM_OK;
 }
 
-static void cam_free(fsim *s);
-static void pts_free(fsim *s);
-static void vox_free(fsim *s);
-static void nrm_free(fsim *s);
-static void flw_free(fsim *s);
-static void ray_free(fsim *s);
-static void probe_free(fsim *s);
-static void pair_free(fsim *s);
-static void frame_free(fsim *s);
-static void dyn_free(fsim *s);
-static void con_free(fsim *s);
-static void wr_free(fsim *s);
-extern "C" void fsim_destroy(fsim_t *s) {
-  if (!s) return;
-  hipSetDevice(s->device);
-  if (s->stream) hipStreamSynchronize(s->stream);
-  cam_free(s);
-  pts_free(s);
-  vox_free(s);
-  nrm_free(s);
-  flw_free(s);
-  ray_free(s);
-  probe_free(s);
-  pair_free(s);
-  frame_free(s);
-  dyn_free(s);
-  con_free(s);
-  wr_free(s);
-  hipFree(s->d_sh_state); hipFree(s->d_sh_obs); hipFree(s->d_sh_prog); hipFree(s->d_sh_serial); hipFree(s->d_tab_serial); hipFree(s->d_sh_jobs);
-  if (s->xfer) { hipStreamSynchronize(s->xfer); hipStreamDestroy(s->xfer); }
-  hipFree(s->d_ly_r[0]); hipFree(s->d_ly_r[1]); hipFree(s->d_ly_r[2]); hipFree(s->d_prev); hipFree(s->d_ovf_list); hipFree(s->d_ovf_list2);
-  hipFree(s->d_ly_mw); hipFree(s->d_defer); hipFree(s->d_mworder); hipFree(s->d_mwn); hipFree(s->d_ecfg);
-  hipFree(s->d_m); hipFree(s->d_ly); hipFree(s->d_model); hipFree(s->d_state); hipFree(s->d_aux); hipFree(s->d_tab_parts); hipFree(s->d_tab_noise); hipFree(s->d_tab_attach); hipFree(s->d_cost); hipFree(s->d_order); hipFree(s->d_dense); hipFree(s->d_pre); hipFree(s->d_init); hipFree(s->d_init_mask); if (s->h_nreset) hipHostFree(s->h_nreset);
-  if (s->ev0) hipEventDestroy(s->ev0);
-  if (s->ev1) hipEventDestroy(s->ev1);
-  if (s->stream) hipStreamDestroy(s->stream);
-  delete s;
-}
-
 extern "C" int fsim_dims(const fsim_t *s, int32_t *nq, int32_t *nv, int32_t *nu, int32_t *dof_action, int32_t *obs_dim, int32_t *info_dim,
                          int32_t *stride) {
   if (!s) FAIL(FSIM_EINVAL, "null handle");
@@ -1084,6 +1045,60 @@ extern "C" int fsim_sync(fsim_t *s) {
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipStreamSynchronize(s->stream));
   return settle(s);
+}
+
+// ---- what the state-sensor families (rays, probes, pairs, frames, dynamics, contacts, wrenches) share on the host
+// The device tables of one sensor state.  The state keeps its typed pointers for the kernels' arguments; this owns what they point to:
+// put() allocates and uploads and, after the first error, does nothing more; release() frees everything put() allocated.
+struct DevTables {
+  std::vector<void *> owned;
+  hipError_t err = hipSuccess;
+  // *d = `words` 4-byte words on the device (at least one, so that no table pointer is NULL), filled from h unless h is NULL
+  template <class T> void put(T **d, const void *h, size_t words) {
+    if (err != hipSuccess) return;
+    void *p = nullptr;
+    if ((err = hipMalloc(&p, std::max(words, (size_t)1) * 4)) != hipSuccess) return;
+    owned.push_back(p);
+    *d = (T *)p;
+    if (h && words) err = hipMemcpy(p, h, words * 4, hipMemcpyHostToDevice);
+  }
+  void release() {
+    for (void *p : owned) hipFree(p);
+    owned.clear();
+  }
+};
+
+// Free a sensor slot of the handle (S: a state with a DevTables `tabs`).  The caller has waited for the stream.
+template <class S> static void sensor_free(S *&slot) {
+  if (!slot) return;
+  slot->tabs.release();
+  delete slot;
+  slot = nullptr;
+}
+
+// fsim_set_X(handle, 0, ...): clear the slot
+template <class S> static int sensor_clear(fsim *s, S *&slot) {
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the tables)
+  sensor_free(slot);
+  return FSIM_OK;
+}
+
+// The tail of every fsim_set_X, after its validation and table building: upload(c.tabs) puts the tables of the local state c on the
+// device, and only a complete upload replaces the slot -- a failed allocation or upload leaves the set before it.  (Old and new tables
+// are on the device together for that moment; the largest is the pose scratch of rays, probes and pairs, n_envs * pstride * 4 bytes.)
+template <class S, class Upload> static int sensor_install(fsim *s, const char *who, S *&slot, S &c, Upload upload) {
+  HIPCHK(hipSetDevice(s->device));
+  { int rc_ = settle(s); if (rc_) return rc_; }
+  HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the old tables)
+  upload(c.tabs);
+  if (c.tabs.err != hipSuccess) {
+    c.tabs.release();
+    FAIL(FSIM_EHIP, "%s: %s", who, hipGetErrorString(c.tabs.err));
+  }
+  sensor_free(slot);
+  slot = new S(c);
+  return FSIM_OK;
 }
 
 static KParams kparams(const fsim *s, int nsub, int mode) {
@@ -1704,3 +1719,31 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
 #include "fsim_dynamics.hpp"
 #include "fsim_contacts.hpp"
 #include "fsim_wrench.hpp"
+
+// (below the sensor files: it frees their states, which are complete types only here)
+extern "C" void fsim_destroy(fsim_t *s) {
+  if (!s) return;
+  hipSetDevice(s->device);
+  if (s->stream) hipStreamSynchronize(s->stream);
+  cam_free(s);
+  pts_free(s);
+  vox_free(s);
+  nrm_free(s);
+  flw_free(s);
+  sensor_free(s->ray);
+  sensor_free(s->probe);
+  sensor_free(s->pair);
+  sensor_free(s->frame);
+  sensor_free(s->dyn);
+  sensor_free(s->con);
+  sensor_free(s->wr);
+  hipFree(s->d_sh_state); hipFree(s->d_sh_obs); hipFree(s->d_sh_prog); hipFree(s->d_sh_serial); hipFree(s->d_tab_serial); hipFree(s->d_sh_jobs);
+  if (s->xfer) { hipStreamSynchronize(s->xfer); hipStreamDestroy(s->xfer); }
+  hipFree(s->d_ly_r[0]); hipFree(s->d_ly_r[1]); hipFree(s->d_ly_r[2]); hipFree(s->d_prev); hipFree(s->d_ovf_list); hipFree(s->d_ovf_list2);
+  hipFree(s->d_ly_mw); hipFree(s->d_defer); hipFree(s->d_mworder); hipFree(s->d_mwn); hipFree(s->d_ecfg);
+  hipFree(s->d_m); hipFree(s->d_ly); hipFree(s->d_model); hipFree(s->d_state); hipFree(s->d_aux); hipFree(s->d_tab_parts); hipFree(s->d_tab_noise); hipFree(s->d_tab_attach); hipFree(s->d_cost); hipFree(s->d_order); hipFree(s->d_dense); hipFree(s->d_pre); hipFree(s->d_init); hipFree(s->d_init_mask); if (s->h_nreset) hipHostFree(s->h_nreset);
+  if (s->ev0) hipEventDestroy(s->ev0);
+  if (s->ev1) hipEventDestroy(s->ev1);
+  if (s->stream) hipStreamDestroy(s->stream);
+  delete s;
+}

@@ -285,6 +285,7 @@ struct CamState {
   float *d_depth = nullptr; int *d_seg = nullptr; // image scratch of the derived observations (cam_render_images), [n_envs * npix]
 };
 
+static void flw_free(fsim *s); // fsim_flow.hpp
 static void cam_free(fsim *s) {
   if (!s->cam) return;
   hipFree(s->cam->d_cams); hipFree(s->cam->d_cg); hipFree(s->cam->d_planes); hipFree(s->cam->d_pose);
@@ -307,6 +308,13 @@ static int cam_mount_tables(const fsim *s, CamMountTables &t) {
     return FSIM_EINVAL;
   if (s->m.agent == 2 && !blob_i(s->blob, "cursor_bodyid", t.cursor_body)) return FSIM_EINVAL;
   return FSIM_OK;
+}
+
+// k_cam_pose's arguments for the handle's model: nframes mounted frames (cameras, sensors) behind the geoms, pstride words per env
+static CamPoseArgs cam_pose_args(const fsim *s, int nframes, int pstride) {
+  const DModel &m = s->m;
+  return CamPoseArgs{m.r_parent, m.r_jtype, m.r_qposadr, m.cg_body, m.cg_cursor, m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.cg_pos, m.cg_mat, m.cursor_pos0,
+                     m.nr, m.maxdepth, m.ncg, nframes, s->ly.stride, s->ly.qpos, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1, pstride};
 }
 
 // One d_cams row (CCW_*) of a frame (pos, quat wxyz) given in the frame of model body `body` (-1: the world), composed in double.
@@ -411,9 +419,7 @@ extern "C" int fsim_render(fsim_t *s, float *depth_dev, int32_t *seg_dev) {
   { int rc_ = settle(s); if (rc_) return rc_; } // the state fsim_sync leaves: overflowed envs re-stepped first
   const CamState &k = *s->cam;
   const DModel &m = s->m;
-  CamPoseArgs pa{m.r_parent, m.r_jtype, m.r_qposadr, m.cg_body, m.cg_cursor, m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.cg_pos, m.cg_mat, m.cursor_pos0,
-                 m.nr, m.maxdepth, m.ncg, k.ncam, s->ly.stride, s->ly.qpos, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1, k.pstride};
-  hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, pa, s->d_state, k.d_cams, k.d_pose);
+  hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, cam_pose_args(s, k.ncam, k.pstride), s->d_state, k.d_cams, k.d_pose);
   HIPCHK(hipGetLastError());
   CamRayArgs ra{};
   ra.ncg = m.ncg; ra.ncam = k.ncam; ra.W = k.W; ra.H = k.H; ra.ntx = (k.W + CAM_TILE - 1) / CAM_TILE; ra.nty = (k.H + CAM_TILE - 1) / CAM_TILE;

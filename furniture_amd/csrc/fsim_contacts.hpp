@@ -138,23 +138,12 @@ template <class Ctx> __global__ __launch_bounds__(64, 2) void k_contact_force(co
 struct ConState {
   int nsens = 0, mw = 0;
   unsigned *d_masks = nullptr; // ConArgs::masks
+  DevTables tabs; // owns it
 };
-
-static void con_free(fsim *s) { // (fsim_set_contacts calls it after its stream wait, fsim_destroy after its own)
-  if (!s->con) return;
-  hipFree(s->con->d_masks);
-  delete s->con;
-  s->con = nullptr;
-}
 
 extern "C" int fsim_set_contacts(fsim_t *s, int n_sensors, const fsim_contact_sensor_t *sensors) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_contacts: null handle");
-  if (n_sensors == 0) { // clear
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the table)
-    con_free(s);
-    return FSIM_OK;
-  }
+  if (n_sensors == 0) return sensor_clear(s, s->con);
   if (!sensors) FAIL(FSIM_EINVAL, "fsim_set_contacts: null argument");
   if (n_sensors < 1 || n_sensors > FSIM_CON_MAX_SENSORS) FAIL(FSIM_EINVAL, "fsim_set_contacts: %d sensors (1 .. %d)", n_sensors, FSIM_CON_MAX_SENSORS);
   if (s->ly.ncon_max > FSIM_CON_MAX_SLOTS) FAIL(FSIM_EINVAL, "fsim_set_contacts: the handle has %d contact slots (the contact-force pass serves at most %d: one slot per lane)", s->ly.ncon_max, FSIM_CON_MAX_SLOTS);
@@ -191,19 +180,7 @@ extern "C" int fsim_set_contacts(fsim_t *s, int n_sensors, const fsim_contact_se
       for (int cg = 0; cg < m.ncg; cg++)
         if (!((A[cg >> 5] >> (cg & 31)) & 1u)) B[cg >> 5] |= 1u << (cg & 31);
   }
-  HIPCHK(hipSetDevice(s->device));
-  { int rc_ = settle(s); if (rc_) return rc_; }
-  HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the old table)
-  // the table is built in a local state and installed once it is complete: a failed allocation or upload leaves the set before it
-  hipError_t e = hipMalloc(&c.d_masks, tab.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(c.d_masks, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(c.d_masks);
-    FAIL(FSIM_EHIP, "fsim_set_contacts: %s", hipGetErrorString(e));
-  }
-  con_free(s);
-  s->con = new ConState(c);
-  return FSIM_OK;
+  return sensor_install(s, "fsim_set_contacts", s->con, c, [&](DevTables &t) { t.put(&c.d_masks, tab.data(), tab.size()); });
 }
 
 extern "C" int fsim_contact_forces(fsim_t *s, const fsim_contact_out_t *out) {

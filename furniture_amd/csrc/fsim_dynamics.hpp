@@ -308,23 +308,12 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
 struct DynState {
   int K = 0, W = 0, maxn = 0;
   int *d_tab = nullptr; // DynArgs::tab
+  DevTables tabs; // owns it
 };
-
-static void dyn_free(fsim *s) { // (fsim_set_dynamics calls it after its stream wait, fsim_destroy after its own)
-  if (!s->dyn) return;
-  hipFree(s->dyn->d_tab);
-  delete s->dyn;
-  s->dyn = nullptr;
-}
 
 extern "C" int fsim_set_dynamics(fsim_t *s, int n_dofs, const int32_t *dofs) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_dynamics: null handle");
-  if (n_dofs == 0) { // clear
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the table)
-    dyn_free(s);
-    return FSIM_OK;
-  }
+  if (n_dofs == 0) return sensor_clear(s, s->dyn);
   if (!dofs) FAIL(FSIM_EINVAL, "fsim_set_dynamics: null argument");
   const DModel &m = s->m;
   if (n_dofs < 1 || n_dofs > m.nv) FAIL(FSIM_EINVAL, "fsim_set_dynamics: %d dofs (1 .. nv = %d)", n_dofs, m.nv);
@@ -356,19 +345,7 @@ extern "C" int fsim_set_dynamics(fsim_t *s, int n_dofs, const int32_t *dofs) {
   }
   for (int i = 0; i < n_dofs; i++) tab[2 * m.nv + i] = dofs[i];
   if ((size_t)12 * c.W > 40 * 1024) FAIL(FSIM_EINVAL, "fsim_set_dynamics: the trees' triangles take %d words (the dynamics pass holds 3 x 3413)", c.W);
-  HIPCHK(hipSetDevice(s->device));
-  { int rc_ = settle(s); if (rc_) return rc_; }
-  HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the old table)
-  // the table is built in a local state and installed once it is complete: a failed allocation or upload leaves the selection before it
-  hipError_t e = hipMalloc(&c.d_tab, tab.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(c.d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(c.d_tab);
-    FAIL(FSIM_EHIP, "fsim_set_dynamics: %s", hipGetErrorString(e));
-  }
-  dyn_free(s);
-  s->dyn = new DynState(c);
-  return FSIM_OK;
+  return sensor_install(s, "fsim_set_dynamics", s->dyn, c, [&](DevTables &t) { t.put(&c.d_tab, tab.data(), tab.size()); });
 }
 
 extern "C" int fsim_dynamics(fsim_t *s, float *mass_dev, float *minv_dev, float *bias_dev, float *gravity_dev) {

@@ -210,8 +210,8 @@ extern "C" int fsim_render_flow(fsim_t *s, float *depth_dev, int32_t *seg_dev, f
   const int *seg;
   { int rc_ = cam_render_images(s, depth_dev, seg_dev, &depth, &seg); if (rc_) return rc_; }
   FlwTwistArgs ta{};
-  ta.p = CamPoseArgs{m.r_parent, m.r_jtype, m.r_qposadr, m.cg_body, m.cg_cursor, m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.cg_pos, m.cg_mat, m.cursor_pos0,
-                     m.nr, m.maxdepth, m.ncg, k.ncam, s->ly.stride, s->ly.qpos, -1, k.pstride};
+  ta.p = cam_pose_args(s, k.ncam, k.pstride);
+  ta.p.ecpos = -1;
   ta.r_dofadr = m.r_dofadr; ta.qvel = s->ly.qvel; ta.tstride = nrow * FLW_TW;
   hipLaunchKernelGGL(k_cam_twist, dim3(s->n_envs), dim3(64), 0, s->stream, ta, s->d_state, k.d_cams, k.d_pose, v.d_twist);
   HIPCHK(hipGetLastError());

@@ -202,23 +202,12 @@ __global__ __launch_bounds__(64) void k_frame_state(FrameArgs a, const float *__
 struct FrameState {
   int nsens = 0;
   float *d_frames = nullptr; // [nsens][2][CCW_WORDS]: the frame's row, then the reference's
+  DevTables tabs; // owns it
 };
-
-static void frame_free(fsim *s) { // (fsim_set_frames calls it after its stream wait, fsim_destroy after its own)
-  if (!s->frame) return;
-  hipFree(s->frame->d_frames);
-  delete s->frame;
-  s->frame = nullptr;
-}
 
 extern "C" int fsim_set_frames(fsim_t *s, int n_sensors, const fsim_frame_sensor_t *sensors) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_frames: null handle");
-  if (n_sensors == 0) { // clear
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the table)
-    frame_free(s);
-    return FSIM_OK;
-  }
+  if (n_sensors == 0) return sensor_clear(s, s->frame);
   if (!sensors) FAIL(FSIM_EINVAL, "fsim_set_frames: null argument");
   if (n_sensors < 1 || n_sensors > FSIM_FRAME_MAX_SENSORS) FAIL(FSIM_EINVAL, "fsim_set_frames: %d sensors (1 .. %d)", n_sensors, FSIM_FRAME_MAX_SENSORS);
   const DModel &m = s->m;
@@ -239,21 +228,9 @@ extern "C" int fsim_set_frames(fsim_t *s, int n_sensors, const fsim_frame_sensor
       if (rb < 0 || rb >= m.nr) FAIL(FSIM_EINVAL, "frame sensor %d: %s: body %d folds into reduced body %d of %d", i, who, f.body, rb, m.nr);
     }
   }
-  HIPCHK(hipSetDevice(s->device));
-  { int rc_ = settle(s); if (rc_) return rc_; }
-  HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the old table)
-  // the table is built in a local state and installed once it is complete: a failed allocation or upload leaves the set before it
   FrameState c;
   c.nsens = n_sensors;
-  hipError_t e = hipMalloc(&c.d_frames, rows.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(c.d_frames, rows.data(), rows.size() * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(c.d_frames);
-    FAIL(FSIM_EHIP, "fsim_set_frames: %s", hipGetErrorString(e));
-  }
-  frame_free(s);
-  s->frame = new FrameState(c);
-  return FSIM_OK;
+  return sensor_install(s, "fsim_set_frames", s->frame, c, [&](DevTables &t) { t.put(&c.d_frames, rows.data(), rows.size()); });
 }
 
 extern "C" int fsim_frame_state(fsim_t *s, float *pos_dev, float *quat_dev, float *vel_dev, float *jac_dev) {

@@ -108,25 +108,12 @@ struct PairState {
   int nsens = 0, npairs = 0, pstride = 0;
   float *d_cg = nullptr, *d_sens = nullptr, *d_pose = nullptr;
   int *d_pairs = nullptr;
+  DevTables tabs; // owns them
 };
-
-static void pair_free_tables(PairState &k) { hipFree(k.d_cg); hipFree(k.d_sens); hipFree(k.d_pose); hipFree(k.d_pairs); }
-
-static void pair_free(fsim *s) { // (fsim_set_pairs calls it after its stream wait, fsim_destroy after its own)
-  if (!s->pair) return;
-  pair_free_tables(*s->pair);
-  delete s->pair;
-  s->pair = nullptr;
-}
 
 extern "C" int fsim_set_pairs(fsim_t *s, int n_sensors, const fsim_pair_sensor_t *sensors) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_pairs: null handle");
-  if (n_sensors == 0) { // clear
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the tables)
-    pair_free(s);
-    return FSIM_OK;
-  }
+  if (n_sensors == 0) return sensor_clear(s, s->pair);
   if (!sensors) FAIL(FSIM_EINVAL, "fsim_set_pairs: null argument");
   if (n_sensors < 1 || n_sensors > FSIM_PAIR_MAX_SENSORS) FAIL(FSIM_EINVAL, "fsim_set_pairs: %d sensors (1 .. %d)", n_sensors, FSIM_PAIR_MAX_SENSORS);
   const DModel &m = s->m;
@@ -178,31 +165,12 @@ extern "C" int fsim_set_pairs(fsim_t *s, int n_sensors, const fsim_pair_sensor_t
   }
   c.npairs = (int)pairs.size();
   c.pstride = (CAM_PW * m.ncg + 3) / 4 * 4;
-  HIPCHK(hipSetDevice(s->device));
-  { int rc_ = settle(s); if (rc_) return rc_; }
-  HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the old tables)
-  pair_free(s);
-  // the tables are built in a local state and installed once they are complete: a failed allocation or upload leaves no pair set
-  PairState &k = c;
-  const auto put = [](float **d, const void *h, size_t words) -> hipError_t { // allocate (at least a word) and copy
-    hipError_t e = hipMalloc(d, std::max(words, (size_t)1) * 4);
-    if (e == hipSuccess && words) e = hipMemcpy(*d, h, words * 4, hipMemcpyHostToDevice);
-    return e;
-  };
-  const auto upload = [&]() -> hipError_t {
-    hipError_t e;
-    if ((e = put(&k.d_sens, srow.data(), srow.size())) != hipSuccess) return e;
-    if ((e = put((float **)&k.d_pairs, pairs.data(), pairs.size())) != hipSuccess) return e;
-    if ((e = put(&k.d_cg, cg.data(), cg.size())) != hipSuccess) return e;
-    return hipMalloc(&k.d_pose, (size_t)s->n_envs * std::max(k.pstride, 4) * 4);
-  };
-  const hipError_t e = upload();
-  if (e != hipSuccess) {
-    pair_free_tables(k);
-    FAIL(FSIM_EHIP, "fsim_set_pairs: %s", hipGetErrorString(e));
-  }
-  s->pair = new PairState(c);
-  return FSIM_OK;
+  return sensor_install(s, "fsim_set_pairs", s->pair, c, [&](DevTables &t) {
+    t.put(&c.d_sens, srow.data(), srow.size());
+    t.put(&c.d_pairs, pairs.data(), pairs.size());
+    t.put(&c.d_cg, cg.data(), cg.size());
+    t.put(&c.d_pose, nullptr, (size_t)s->n_envs * std::max(c.pstride, 4));
+  });
 }
 
 extern "C" int fsim_pair_distance(fsim_t *s, float *dist_dev, int32_t *geoms_dev, float *fromto_dev, float *normal_dev) {
@@ -213,9 +181,7 @@ extern "C" int fsim_pair_distance(fsim_t *s, float *dist_dev, int32_t *geoms_dev
   { int rc_ = settle(s); if (rc_) return rc_; } // the state fsim_sync leaves: overflowed envs re-stepped first
   const PairState &k = *s->pair;
   const DModel &m = s->m;
-  CamPoseArgs pa{m.r_parent, m.r_jtype, m.r_qposadr, m.cg_body, m.cg_cursor, m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.cg_pos, m.cg_mat, m.cursor_pos0,
-                 m.nr, m.maxdepth, m.ncg, 0 /* no frames */, s->ly.stride, s->ly.qpos, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1, k.pstride};
-  hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, pa, s->d_state, (const float *)nullptr, k.d_pose);
+  hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, cam_pose_args(s, 0 /* no frames */, k.pstride), s->d_state, (const float *)nullptr, k.d_pose);
   HIPCHK(hipGetLastError());
   PairArgs ra{};
   ra.ncg = m.ncg; ra.nsens = k.nsens; ra.pstride = k.pstride;

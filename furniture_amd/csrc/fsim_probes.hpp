@@ -199,19 +199,8 @@ struct ProbeState {
   int nsens = 0, nprobes = 0, nplanes = 0, pstride = 0, njobs = 0;
   float *d_mounts = nullptr, *d_cg = nullptr, *d_planes = nullptr, *d_kap = nullptr, *d_pose = nullptr, *d_sens = nullptr, *d_pts = nullptr, *d_jsph = nullptr;
   int *d_jobs = nullptr;
+  DevTables tabs; // owns them
 };
-
-static void prb_free_tables(ProbeState &k) {
-  hipFree(k.d_mounts); hipFree(k.d_cg); hipFree(k.d_planes); hipFree(k.d_kap); hipFree(k.d_pose); hipFree(k.d_sens); hipFree(k.d_pts); hipFree(k.d_jsph);
-  hipFree(k.d_jobs);
-}
-
-static void probe_free(fsim *s) { // (fsim_set_probes calls it after its stream wait, fsim_destroy after its own)
-  if (!s->probe) return;
-  prb_free_tables(*s->probe);
-  delete s->probe;
-  s->probe = nullptr;
-}
 
 // The bound factor of a hull (file comment): min over unit u of max_i n_i . u over the planes that touch the sphere's inside (c_i <= rb),
 // evaluated on a latitude / longitude grid of step D and lowered by the grid's covering radius (any u is within D / 2 in each angle of a
@@ -243,12 +232,7 @@ static float prb_hull_kappa(const float *planes, int num, float rb) {
 extern "C" int fsim_set_probes(fsim_t *s, int n_sensors, const fsim_probe_sensor_t *sensors, int n_probes, const float *pts, int n_planes,
                                const float *hull_planes, const int32_t *hull_adr, const int32_t *hull_num) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_probes: null handle");
-  if (n_sensors == 0) { // clear
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the tables)
-    probe_free(s);
-    return FSIM_OK;
-  }
+  if (n_sensors == 0) return sensor_clear(s, s->probe);
   if (!sensors || !pts) FAIL(FSIM_EINVAL, "fsim_set_probes: null argument");
   if (n_sensors < 1 || n_sensors > FSIM_PROBE_MAX_SENSORS) FAIL(FSIM_EINVAL, "fsim_set_probes: %d sensors (1 .. %d)", n_sensors, FSIM_PROBE_MAX_SENSORS);
   if (n_probes < 1 || n_probes > FSIM_PROBE_MAX_PROBES) FAIL(FSIM_EINVAL, "fsim_set_probes: %d probes (1 .. %d over all sensors)", n_probes, FSIM_PROBE_MAX_PROBES);
@@ -301,36 +285,17 @@ extern "C" int fsim_set_probes(fsim_t *s, int n_sensors, const fsim_probe_sensor
     if (mt.cg_type[g] == GT_MESH) kap[g] = prb_hull_kappa(hull_planes + 4 * (size_t)hull_adr[g], hull_num[g], mt.cg_rbound[g]);
   c.njobs = (int)jobs.size() / 3;
   c.pstride = (CAM_PW * (m.ncg + n_sensors) + 3) / 4 * 4;
-  HIPCHK(hipSetDevice(s->device));
-  { int rc_ = settle(s); if (rc_) return rc_; }
-  HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the old tables)
-  probe_free(s);
-  // the tables are built in a local state and installed once they are complete: a failed allocation or upload leaves no probe set
-  ProbeState &k = c;
-  const auto put = [](float **d, const void *h, size_t words) -> hipError_t { // allocate (at least a word) and copy
-    hipError_t e = hipMalloc(d, std::max(words, (size_t)1) * 4);
-    if (e == hipSuccess && words) e = hipMemcpy(*d, h, words * 4, hipMemcpyHostToDevice);
-    return e;
-  };
-  const auto upload = [&]() -> hipError_t {
-    hipError_t e;
-    if ((e = put(&k.d_mounts, mrow.data(), mrow.size())) != hipSuccess) return e;
-    if ((e = put(&k.d_sens, srow.data(), srow.size())) != hipSuccess) return e;
-    if ((e = put(&k.d_pts, pts, (size_t)3 * n_probes)) != hipSuccess) return e;
-    if ((e = put((float **)&k.d_jobs, jobs.data(), jobs.size())) != hipSuccess) return e;
-    if ((e = put(&k.d_jsph, jsph.data(), jsph.size())) != hipSuccess) return e;
-    if ((e = put(&k.d_cg, cg.data(), cg.size())) != hipSuccess) return e;
-    if ((e = put(&k.d_kap, kap.data(), kap.size())) != hipSuccess) return e;
-    if ((e = put(&k.d_planes, hull_planes, (size_t)4 * n_planes)) != hipSuccess) return e;
-    return hipMalloc(&k.d_pose, (size_t)s->n_envs * k.pstride * 4);
-  };
-  const hipError_t e = upload();
-  if (e != hipSuccess) {
-    prb_free_tables(k);
-    FAIL(FSIM_EHIP, "fsim_set_probes: %s", hipGetErrorString(e));
-  }
-  s->probe = new ProbeState(c);
-  return FSIM_OK;
+  return sensor_install(s, "fsim_set_probes", s->probe, c, [&](DevTables &t) {
+    t.put(&c.d_mounts, mrow.data(), mrow.size());
+    t.put(&c.d_sens, srow.data(), srow.size());
+    t.put(&c.d_pts, pts, (size_t)3 * n_probes);
+    t.put(&c.d_jobs, jobs.data(), jobs.size());
+    t.put(&c.d_jsph, jsph.data(), jsph.size());
+    t.put(&c.d_cg, cg.data(), cg.size());
+    t.put(&c.d_kap, kap.data(), kap.size());
+    t.put(&c.d_planes, hull_planes, (size_t)4 * n_planes);
+    t.put(&c.d_pose, nullptr, (size_t)s->n_envs * c.pstride);
+  });
 }
 
 extern "C" int fsim_probe_distance(fsim_t *s, float *dist_dev, int32_t *geom_dev, float *grad_dev) {
@@ -341,9 +306,7 @@ extern "C" int fsim_probe_distance(fsim_t *s, float *dist_dev, int32_t *geom_dev
   { int rc_ = settle(s); if (rc_) return rc_; } // the state fsim_sync leaves: overflowed envs re-stepped first
   const ProbeState &k = *s->probe;
   const DModel &m = s->m;
-  CamPoseArgs pa{m.r_parent, m.r_jtype, m.r_qposadr, m.cg_body, m.cg_cursor, m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.cg_pos, m.cg_mat, m.cursor_pos0,
-                 m.nr, m.maxdepth, m.ncg, k.nsens, s->ly.stride, s->ly.qpos, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1, k.pstride};
-  hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, pa, s->d_state, k.d_mounts, k.d_pose);
+  hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, cam_pose_args(s, k.nsens, k.pstride), s->d_state, k.d_mounts, k.d_pose);
   HIPCHK(hipGetLastError());
   ProbeArgs ra{};
   ra.ncg = m.ncg; ra.nprobes = k.nprobes; ra.nplanes = k.nplanes; ra.pstride = k.pstride; ra.njobs = k.njobs;

@@ -110,25 +110,13 @@ struct RayState {
   int nsens = 0, nrays = 0, nplanes = 0, pstride = 0, njobs = 0;
   float *d_mounts = nullptr, *d_cg = nullptr, *d_planes = nullptr, *d_pose = nullptr, *d_sens = nullptr, *d_dirs = nullptr;
   int *d_jobs = nullptr;
+  DevTables tabs; // owns them
 };
-
-static void ray_free(fsim *s) { // (fsim_set_rays calls it after its stream wait, fsim_destroy after its own)
-  if (!s->ray) return;
-  RayState &k = *s->ray;
-  hipFree(k.d_mounts); hipFree(k.d_cg); hipFree(k.d_planes); hipFree(k.d_pose); hipFree(k.d_sens); hipFree(k.d_dirs); hipFree(k.d_jobs);
-  delete s->ray;
-  s->ray = nullptr;
-}
 
 extern "C" int fsim_set_rays(fsim_t *s, int n_sensors, const fsim_ray_sensor_t *sensors, int n_rays, const float *dirs, int n_planes,
                              const float *hull_planes, const int32_t *hull_adr, const int32_t *hull_num) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_rays: null handle");
-  if (n_sensors == 0) { // clear
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream)); // (a cast in flight still reads the tables)
-    ray_free(s);
-    return FSIM_OK;
-  }
+  if (n_sensors == 0) return sensor_clear(s, s->ray);
   if (!sensors || !dirs) FAIL(FSIM_EINVAL, "fsim_set_rays: null argument");
   if (n_sensors < 1 || n_sensors > FSIM_RAY_MAX_SENSORS) FAIL(FSIM_EINVAL, "fsim_set_rays: %d sensors (1 .. %d)", n_sensors, FSIM_RAY_MAX_SENSORS);
   if (n_rays < 1 || n_rays > FSIM_RAY_MAX_RAYS) FAIL(FSIM_EINVAL, "fsim_set_rays: %d rays (1 .. %d over all sensors)", n_rays, FSIM_RAY_MAX_RAYS);
@@ -168,36 +156,15 @@ extern "C" int fsim_set_rays(fsim_t *s, int n_sensors, const fsim_ray_sensor_t *
   { int rc_ = cam_geom_rows(m, mt, "fsim_set_rays", n_planes, hull_planes, hull_adr, hull_num, cg); if (rc_) return rc_; }
   c.njobs = (int)jobs.size() / 3;
   c.pstride = (CAM_PW * (m.ncg + n_sensors) + 3) / 4 * 4;
-  HIPCHK(hipSetDevice(s->device));
-  { int rc_ = settle(s); if (rc_) return rc_; }
-  HIPCHK(hipStreamSynchronize(s->stream)); // (a cast in flight still reads the old tables)
-  ray_free(s);
-  // the tables are built in a local state and installed once they are complete: a failed allocation or upload leaves no ray set
-  RayState &k = c;
-  const auto upload = [&]() -> hipError_t {
-    hipError_t e;
-    if ((e = hipMalloc(&k.d_mounts, mrow.size() * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&k.d_sens, srow.size() * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&k.d_dirs, udir.size() * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&k.d_jobs, jobs.size() * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&k.d_cg, std::max(cg.size(), (size_t)1) * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&k.d_planes, (size_t)4 * std::max(n_planes, 1) * 4)) != hipSuccess) return e;
-    if ((e = hipMalloc(&k.d_pose, (size_t)s->n_envs * k.pstride * 4)) != hipSuccess) return e;
-    if ((e = hipMemcpy(k.d_mounts, mrow.data(), mrow.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if ((e = hipMemcpy(k.d_sens, srow.data(), srow.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if ((e = hipMemcpy(k.d_dirs, udir.data(), udir.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if ((e = hipMemcpy(k.d_jobs, jobs.data(), jobs.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if (!cg.empty() && (e = hipMemcpy(k.d_cg, cg.data(), cg.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if (n_planes && (e = hipMemcpy(k.d_planes, hull_planes, (size_t)16 * n_planes, hipMemcpyHostToDevice)) != hipSuccess) return e;
-    return hipSuccess;
-  };
-  const hipError_t e = upload();
-  if (e != hipSuccess) {
-    hipFree(k.d_mounts); hipFree(k.d_cg); hipFree(k.d_planes); hipFree(k.d_pose); hipFree(k.d_sens); hipFree(k.d_dirs); hipFree(k.d_jobs);
-    FAIL(FSIM_EHIP, "fsim_set_rays: %s", hipGetErrorString(e));
-  }
-  s->ray = new RayState(c);
-  return FSIM_OK;
+  return sensor_install(s, "fsim_set_rays", s->ray, c, [&](DevTables &t) {
+    t.put(&c.d_mounts, mrow.data(), mrow.size());
+    t.put(&c.d_sens, srow.data(), srow.size());
+    t.put(&c.d_dirs, udir.data(), udir.size());
+    t.put(&c.d_jobs, jobs.data(), jobs.size());
+    t.put(&c.d_cg, cg.data(), cg.size());
+    t.put(&c.d_planes, hull_planes, (size_t)4 * n_planes);
+    t.put(&c.d_pose, nullptr, (size_t)s->n_envs * c.pstride);
+  });
 }
 
 extern "C" int fsim_cast_rays(fsim_t *s, float *dist_dev, int32_t *geom_dev, float *normal_dev) {
@@ -208,9 +175,7 @@ extern "C" int fsim_cast_rays(fsim_t *s, float *dist_dev, int32_t *geom_dev, flo
   { int rc_ = settle(s); if (rc_) return rc_; } // the state fsim_sync leaves: overflowed envs re-stepped first
   const RayState &k = *s->ray;
   const DModel &m = s->m;
-  CamPoseArgs pa{m.r_parent, m.r_jtype, m.r_qposadr, m.cg_body, m.cg_cursor, m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.cg_pos, m.cg_mat, m.cursor_pos0,
-                 m.nr, m.maxdepth, m.ncg, k.nsens, s->ly.stride, s->ly.qpos, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1, k.pstride};
-  hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, pa, s->d_state, k.d_mounts, k.d_pose);
+  hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, cam_pose_args(s, k.nsens, k.pstride), s->d_state, k.d_mounts, k.d_pose);
   HIPCHK(hipGetLastError());
   RayArgs ra{};
   ra.ncg = m.ncg; ra.nrays = k.nrays; ra.nplanes = k.nplanes; ra.pstride = k.pstride; ra.njobs = k.njobs;

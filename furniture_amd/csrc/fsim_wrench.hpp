@@ -283,23 +283,12 @@ template <class Ctx> __global__ __launch_bounds__(64, 2) void k_wrench(const DMo
 struct WrState {
   int nsens = 0;
   float *d_rows = nullptr; // WrArgs::rows
+  DevTables tabs; // owns it
 };
-
-static void wr_free(fsim *s) { // (fsim_set_wrenches calls it after its stream wait, fsim_destroy after its own)
-  if (!s->wr) return;
-  hipFree(s->wr->d_rows);
-  delete s->wr;
-  s->wr = nullptr;
-}
 
 extern "C" int fsim_set_wrenches(fsim_t *s, int n_sensors, const fsim_wrench_sensor_t *sensors) {
   if (!s) FAIL(FSIM_EINVAL, "fsim_set_wrenches: null handle");
-  if (n_sensors == 0) { // clear
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the table)
-    wr_free(s);
-    return FSIM_OK;
-  }
+  if (n_sensors == 0) return sensor_clear(s, s->wr);
   if (!sensors) FAIL(FSIM_EINVAL, "fsim_set_wrenches: null argument");
   if (n_sensors < 1 || n_sensors > FSIM_WRENCH_MAX_SENSORS) FAIL(FSIM_EINVAL, "fsim_set_wrenches: %d sensors (1 .. %d)", n_sensors, FSIM_WRENCH_MAX_SENSORS);
   if (s->ly.ncon_max > FSIM_WRENCH_MAX_SLOTS) FAIL(FSIM_EINVAL, "fsim_set_wrenches: the handle has %d contact slots (the wrench pass serves at most %d: one slot per lane)", s->ly.ncon_max, FSIM_WRENCH_MAX_SLOTS);
@@ -316,21 +305,9 @@ extern "C" int fsim_set_wrenches(fsim_t *s, int n_sensors, const fsim_wrench_sen
     const int rb = __builtin_bit_cast(int, r[CCW_RBODY]);
     if (rb <= 0 || rb >= m.nr || __builtin_bit_cast(int, r[CCW_CURSOR]) >= 0) FAIL(FSIM_EINVAL, "wrench sensor %d: body %d does not move (it is fixed in the world)", i, k.body);
   }
-  HIPCHK(hipSetDevice(s->device));
-  { int rc_ = settle(s); if (rc_) return rc_; }
-  HIPCHK(hipStreamSynchronize(s->stream)); // (a launch in flight still reads the old table)
-  // the table is built in a local state and installed once it is complete: a failed allocation or upload leaves the set before it
   WrState c;
   c.nsens = n_sensors;
-  hipError_t e = hipMalloc(&c.d_rows, rows.size() * 4);
-  if (e == hipSuccess) e = hipMemcpy(c.d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    hipFree(c.d_rows);
-    FAIL(FSIM_EHIP, "fsim_set_wrenches: %s", hipGetErrorString(e));
-  }
-  wr_free(s);
-  s->wr = new WrState(c);
-  return FSIM_OK;
+  return sensor_install(s, "fsim_set_wrenches", s->wr, c, [&](DevTables &t) { t.put(&c.d_rows, rows.data(), rows.size()); });
 }
 
 extern "C" int fsim_wrenches(fsim_t *s, const fsim_wrench_out_t *out) {

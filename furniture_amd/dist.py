@@ -87,20 +87,10 @@ def step_wait_and_gather(sim, obs, reward, done, tag=0, stream=None, group=None)
         raise NotImplementedError("step_wait_and_gather: normal / shaded images are not part of the multi-GPU gather; render them on each rank instead")
     if getattr(sim, "flow", None) is not None:
         raise NotImplementedError("step_wait_and_gather: flow / velocity images are not part of the multi-GPU gather; render them on each rank instead")
-    if getattr(sim, "rays", None) is not None:
-        raise NotImplementedError("step_wait_and_gather: ray-sensor outputs are not part of the multi-GPU gather; cast them on each rank instead")
-    if getattr(sim, "probes", None) is not None:
-        raise NotImplementedError("step_wait_and_gather: distance-probe outputs are not part of the multi-GPU gather; compute them on each rank instead")
-    if getattr(sim, "pairs", None) is not None:
-        raise NotImplementedError("step_wait_and_gather: pair-distance outputs are not part of the multi-GPU gather; compute them on each rank instead")
-    if getattr(sim, "frames", None) is not None:
-        raise NotImplementedError("step_wait_and_gather: frame-sensor outputs are not part of the multi-GPU gather; compute them on each rank instead")
-    if getattr(sim, "dyn", None) is not None:
-        raise NotImplementedError("step_wait_and_gather: dynamics tensors are not part of the multi-GPU gather; compute them on each rank instead")
-    if getattr(sim, "contacts", None) is not None:
-        raise NotImplementedError("step_wait_and_gather: contact-force outputs are not part of the multi-GPU gather; compute them on each rank instead")
-    if getattr(sim, "wrench_set", None) is not None:
-        raise NotImplementedError("step_wait_and_gather: wrench-sensor outputs are not part of the multi-GPU gather; compute them on each rank instead")
+    from .envs import SENSOR_FAMILIES
+    for f in SENSOR_FAMILIES:
+        if getattr(sim, f.attr, None) is not None:
+            raise NotImplementedError("step_wait_and_gather: %s are not part of the multi-GPU gather; %s them on each rank instead" % (f.gathered, f.verb))
     sim.sync()
     out = gather_observations(obs, reward, done, tag=tag, stream=stream, group=group)
     if stream is not None and obs.is_cuda:

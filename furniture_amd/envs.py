@@ -10,9 +10,10 @@ Everything numeric happens in libfsim.so; this file is plumbing (config intake, 
 reference's RNG stream, tensor allocation).  No CPU fallback: without the HIP library / a GPU construction raises.
 """
 
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from types import SimpleNamespace
 
+import importlib
 import math
 
 import numpy as np
@@ -24,6 +25,20 @@ from .dense import DENSE_COEF_DEFAULTS, pack_dense
 from .sim import (FSim, INFO_OVERFLOW, INFO_CONNECTED_THIS_STEP, INFO_DENSE_PHASE, INFO_DIM, INFO_EPISODE_LENGTH, INFO_FAIL, INFO_LAST_SITE1, INFO_LAST_SITE2,
                   INFO_NEEDS_TABLE, INFO_NUM_CONNECTED, INFO_SUBTASK1, INFO_SUCCESS, INFO_SUCCESS_REWARD_F, INFO_TOUCH_REWARD_F,
                   INFO_PICK_REWARD_F, INFO_CTRL_PENALTY_F, N_NOISE, default_config)
+
+# The state-sensor families, in the order of their keys in the observation dict.  kw: the constructor's keyword and the env's attribute;
+# module: where the spec class `cls` and its check() live; attr, set, shapes, call: FSim's attribute and methods; buf: the env's output
+# buffers.  noun, one, gathered, verb: the family's words in the refusals of the VecEnv wrapper, the mixed batch and the multi-GPU gather.
+SensorFamily = namedtuple("SensorFamily", "kw module cls attr set shapes call buf noun one gathered verb")
+SENSOR_FAMILIES = (
+    SensorFamily("rays", "rays", "RaySet", "rays", "set_rays", "ray_shapes", "cast_rays", "_ray_out", "ray", "ray set", "ray-sensor outputs", "cast"),
+    SensorFamily("probes", "probes", "ProbeSet", "probes", "set_probes", "probe_shapes", "probe_distance", "_probe_out", "probe", "probe set", "distance-probe outputs", "compute"),
+    SensorFamily("pairs", "pairs", "PairSet", "pairs", "set_pairs", "pair_shapes", "pair_distance", "_pair_out", "pair", "pair set", "pair-distance outputs", "compute"),
+    SensorFamily("frames", "frames", "FrameSet", "frames", "set_frames", "frame_shapes", "frame_state", "_frame_out", "frame", "frame set", "frame-sensor outputs", "compute"),
+    SensorFamily("dynamics", "dynamics", "Dynamics", "dyn", "set_dynamics", "dynamics_shapes", "dynamics", "_dyn_out", "dynamics", "dof selection", "dynamics tensors", "compute"),
+    SensorFamily("contacts", "contacts", "ContactSet", "contacts", "set_contacts", "contact_shapes", "contact_forces", "_con_out", "contact", "contact set", "contact-force outputs", "compute"),
+    SensorFamily("wrenches", "wrench", "WrenchSet", "wrench_set", "set_wrenches", "wrench_shapes", "wrenches", "_wr_out", "wrench", "wrench set", "wrench-sensor outputs", "compute"),
+)
 
 # furniture/config/furniture.py defaults that matter on the hot path (file:line in the reference)
 DEFAULTS = dict(
@@ -441,27 +456,10 @@ class FurnitureBatchEnv:
         if flow is not None:
             from .flow import check as check_flow
             check_flow(flow, list(cameras) if cameras else None)
-        if rays is not None:
-            from .rays import check as check_rays
-            check_rays(rays)
-        if probes is not None:
-            from .probes import check as check_probes
-            check_probes(probes)
-        if pairs is not None:
-            from .pairs import check as check_pairs
-            check_pairs(pairs)
-        if frames is not None:
-            from .frames import check as check_frames
-            check_frames(frames)
-        if dynamics is not None:
-            from .dynamics import check as check_dynamics
-            check_dynamics(dynamics)
-        if contacts is not None:
-            from .contacts import check as check_contacts
-            check_contacts(contacts)
-        if wrenches is not None:
-            from .wrench import check as check_wrenches
-            check_wrenches(wrenches)
+        sensors = dict(rays=rays, probes=probes, pairs=pairs, frames=frames, dynamics=dynamics, contacts=contacts, wrenches=wrenches)
+        for f in SENSOR_FAMILIES:
+            if sensors[f.kw] is not None:
+                importlib.import_module("." + f.module, __package__).check(sensors[f.kw])
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -578,34 +576,11 @@ class FurnitureBatchEnv:
                 for k, (sh, dt) in shapes().items():
                     out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
                 setattr(self, bufs, out)
-        self.rays = rays
-        if rays is not None:  # (without rays: no allocation, no launch, the same observation dict)
-            self.sim.set_rays(rays)
-            self._ray_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.ray_shapes().items()}
-        self.probes = probes
-        if probes is not None:  # (without probes: no allocation, no launch, the same observation dict)
-            self.sim.set_probes(probes)
-            self._probe_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.probe_shapes().items()}
-        self.pairs = pairs
-        if pairs is not None:  # (without pairs: no allocation, no launch, the same observation dict)
-            self.sim.set_pairs(pairs)
-            self._pair_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.pair_shapes().items()}
-        self.frames = frames
-        if frames is not None:  # (without frames: no allocation, no launch, the same observation dict)
-            self.sim.set_frames(frames)
-            self._frame_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.frame_shapes().items()}
-        self.dynamics = dynamics
-        if dynamics is not None:  # (without dynamics: no allocation, no launch, the same observation dict)
-            self.sim.set_dynamics(dynamics)
-            self._dyn_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.dynamics_shapes().items()}
-        self.contacts = contacts
-        if contacts is not None:  # (without contacts: no allocation, no launch, the same observation dict)
-            self.sim.set_contacts(contacts)
-            self._con_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.contact_shapes().items()}
-        self.wrenches = wrenches
-        if wrenches is not None:  # (without wrenches: no allocation, no launch, the same observation dict)
-            self.sim.set_wrenches(wrenches)
-            self._wr_out = {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in self.sim.wrench_shapes().items()}
+        for f in SENSOR_FAMILIES:  # (without a family: no allocation, no launch, the same observation dict)
+            setattr(self, f.kw, sensors[f.kw])
+            if sensors[f.kw] is not None:
+                getattr(self.sim, f.set)(sensors[f.kw])
+                setattr(self, f.buf, {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in getattr(self.sim, f.shapes)().items()})
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -651,50 +626,19 @@ class FurnitureBatchEnv:
                 sp.append(("camera_velocity", spaces.Box(-np.inf, np.inf, shape=shape + (3,), dtype=np.float32)))
             if self.flow.velocity and self.point_cloud is not None:
                 sp.append(("point_cloud_velocity", spaces.Box(-np.inf, np.inf, shape=per + (3,), dtype=np.float32)))
-        if self.rays is not None:
-            r = self.rays.n_rays
-            sp.append(("ray_distance", spaces.Box(-1.0, np.inf, shape=(r,), dtype=np.float32)))
-            sp.append(("ray_geom", spaces.Box(-1, self.model.ngeom - 1, shape=(r,), dtype=np.int32)))
-            if self.rays.normal:
-                sp.append(("ray_normal", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
-        if self.probes is not None:
-            r = self.probes.n_probes
-            sp.append(("probe_distance", spaces.Box(-np.inf, max(k.dmax for k in self.probes.sensors), shape=(r,), dtype=np.float32)))
-            sp.append(("probe_geom", spaces.Box(-1, self.model.ngeom - 1, shape=(r,), dtype=np.int32)))
-            if self.probes.gradient:
-                sp.append(("probe_gradient", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
-        if self.pairs is not None:
-            r = self.pairs.n_sensors
-            sp.append(("pair_distance", spaces.Box(-np.inf, max(k.dmax for k in self.pairs.sensors), shape=(r,), dtype=np.float32)))
-            sp.append(("pair_geoms", spaces.Box(-1, self.model.ngeom - 1, shape=(r, 2), dtype=np.int32)))
-            if self.pairs.fromto:
-                sp.append(("pair_fromto", spaces.Box(-np.inf, np.inf, shape=(r, 6), dtype=np.float32)))
-            if self.pairs.normal:
-                sp.append(("pair_normal", spaces.Box(-1.0, 1.0, shape=(r, 3), dtype=np.float32)))
-        if self.frames is not None:
-            r = self.frames.n_sensors
-            sp.append(("frame_pos", spaces.Box(-np.inf, np.inf, shape=(r, 3), dtype=np.float32)))
-            sp.append(("frame_quat", spaces.Box(-np.inf, np.inf, shape=(r, 4), dtype=np.float32)))  # (a unit quaternion up to float32 rounding)
-            if self.frames.velocity:
-                sp.append(("frame_vel", spaces.Box(-np.inf, np.inf, shape=(r, 6), dtype=np.float32)))
-            if self.frames.jacobian:
-                sp.append(("frame_jac", spaces.Box(-np.inf, np.inf, shape=(r, 6, self.model.nv), dtype=np.float32)))
-        if self.dynamics is not None:
-            for k, (sh, _) in self.sim.dynamics_shapes().items():
-                sp.append((k, spaces.Box(-np.inf, np.inf, shape=sh, dtype=np.float32)))
-        if self.contacts is not None:
-            for k, (sh, dt) in self.sim.contact_shapes().items():
-                if dt == self.sim.torch.float32:
-                    sp.append((k, spaces.Box(0.0 if k in ("contact_touch", "con_fn") else -np.inf, np.inf, shape=sh, dtype=np.float32)))
-                else:  # contact_count, contact_status, con_geoms
-                    lo, hi = {"contact_count": (0, self.sim.max_contacts), "contact_status": (0, 3), "con_geoms": (-1, self.model.ngeom - 1)}[k]
-                    sp.append((k, spaces.Box(lo, hi, shape=sh, dtype=np.int32)))
-        if self.wrenches is not None:
-            for k, (sh, dt) in self.sim.wrench_shapes().items():
-                if dt == self.sim.torch.float32:
-                    sp.append((k, spaces.Box(-np.inf, np.inf, shape=sh, dtype=np.float32)))
-                else:  # wrench_status
-                    sp.append((k, spaces.Box(0, 3, shape=sh, dtype=np.int32)))
+        # the state sensors: keys, shapes and dtypes as FSim's X_shapes() give them; the bounds of a key that has any are here
+        dmax = lambda s: max(k.dmax for k in s.sensors) if s is not None else np.inf
+        geom, unit, force, status = (-1, self.model.ngeom - 1), (-1.0, 1.0), (0.0, np.inf), (0, 3)
+        bounds = {"ray_distance": (-1.0, np.inf), "ray_geom": geom, "ray_normal": unit,
+                  "probe_distance": (-np.inf, dmax(self.probes)), "probe_geom": geom, "probe_gradient": unit,
+                  "pair_distance": (-np.inf, dmax(self.pairs)), "pair_geoms": geom, "pair_normal": unit,
+                  "contact_touch": force, "con_fn": force, "contact_count": (0, self.sim.max_contacts), "contact_status": status, "con_geoms": geom,
+                  "wrench_status": status}  # (frame_quat: a unit quaternion up to float32 rounding, so unbounded like the rest)
+        for f in SENSOR_FAMILIES:
+            if getattr(self, f.kw) is not None:
+                for k, (sh, dt) in getattr(self.sim, f.shapes)().items():
+                    lo, hi = bounds.get(k, (-np.inf, np.inf))
+                    sp.append((k, spaces.Box(lo, hi, shape=sh, dtype=np.float32 if dt == self.sim.torch.float32 else np.int32)))
         return spaces.Dict(sp)
 
     def geom_labels(self):
@@ -739,20 +683,9 @@ class FurnitureBatchEnv:
                 out["point_cloud_velocity"] = self._at_points(res["camera_velocity"])
         if self.cameras and self.point_cloud is None and self.voxels is None and self.normals is None and self.flow is None:
             out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
-        if self.rays is not None:  # one fsim_cast_rays call; independent of the cameras
-            out.update(self.sim.cast_rays(out=self._ray_out))
-        if self.probes is not None:  # one fsim_probe_distance call; independent of the cameras and the rays
-            out.update(self.sim.probe_distance(out=self._probe_out))
-        if self.pairs is not None:  # one fsim_pair_distance call; independent of the cameras, the rays and the probes
-            out.update(self.sim.pair_distance(out=self._pair_out))
-        if self.frames is not None:  # one fsim_frame_state call; independent of all the others
-            out.update(self.sim.frame_state(out=self._frame_out))
-        if self.dynamics is not None:  # one fsim_dynamics call; independent of all the others
-            out.update(self.sim.dynamics(out=self._dyn_out))
-        if self.contacts is not None:  # one fsim_contact_forces call; independent of all the others, reads the records only
-            out.update(self.sim.contact_forces(out=self._con_out))
-        if self.wrenches is not None:  # one fsim_wrenches call; independent of all the others, reads the records only
-            out.update(self.sim.wrenches(out=self._wr_out))
+        for f in SENSOR_FAMILIES:  # one library call each; independent of the cameras and of each other, they read the records only
+            if getattr(self, f.kw) is not None:
+                out.update(getattr(self.sim, f.call)(out=getattr(self, f.buf)))
         return out
 
     def _at_points(self, image):
@@ -1097,8 +1030,8 @@ class _SingleEnv:
             dev = old.sim.device.index or 0
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
-                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow, rays=old.rays,
-                                         probes=old.probes, pairs=old.pairs, frames=old.frames, dynamics=old.dynamics, contacts=old.contacts, wrenches=old.wrenches)
+                                         point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow,
+                                         **{f.kw: getattr(old, f.kw) for f in SENSOR_FAMILIES})
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

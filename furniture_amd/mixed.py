@@ -18,7 +18,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .envs import FurnitureBatchEnv, make_config
+from .envs import SENSOR_FAMILIES, FurnitureBatchEnv, make_config
 
 
 def lane_assignment(num_envs, k, first_env_index=0):
@@ -53,27 +53,10 @@ class FurnitureMixedBatchEnv:
         if kw.pop("flow", None) is not None:
             raise NotImplementedError("flow= is not supported by the mixed-furniture batch (one camera set per FurnitureBatchEnv): "
                                       "make one FurnitureBatchEnv per furniture instead")
-        if kw.pop("rays", None) is not None:
-            raise NotImplementedError("rays= is not supported by the mixed-furniture batch (one ray set per FurnitureBatchEnv): "
-                                      "make one FurnitureBatchEnv per furniture instead")
-        if kw.pop("probes", None) is not None:
-            raise NotImplementedError("probes= is not supported by the mixed-furniture batch (one probe set per FurnitureBatchEnv): "
-                                      "make one FurnitureBatchEnv per furniture instead")
-        if kw.pop("pairs", None) is not None:
-            raise NotImplementedError("pairs= is not supported by the mixed-furniture batch (one pair set per FurnitureBatchEnv): "
-                                      "make one FurnitureBatchEnv per furniture instead")
-        if kw.pop("frames", None) is not None:
-            raise NotImplementedError("frames= is not supported by the mixed-furniture batch (one frame set per FurnitureBatchEnv): "
-                                      "make one FurnitureBatchEnv per furniture instead")
-        if kw.pop("dynamics", None) is not None:
-            raise NotImplementedError("dynamics= is not supported by the mixed-furniture batch (one dof selection per FurnitureBatchEnv): "
-                                      "make one FurnitureBatchEnv per furniture instead")
-        if kw.pop("contacts", None) is not None:
-            raise NotImplementedError("contacts= is not supported by the mixed-furniture batch (one contact set per FurnitureBatchEnv): "
-                                      "make one FurnitureBatchEnv per furniture instead")
-        if kw.pop("wrenches", None) is not None:
-            raise NotImplementedError("wrenches= is not supported by the mixed-furniture batch (one wrench set per FurnitureBatchEnv): "
-                                      "make one FurnitureBatchEnv per furniture instead")
+        for f in SENSOR_FAMILIES:
+            if kw.pop(f.kw, None) is not None:
+                raise NotImplementedError("%s= is not supported by the mixed-furniture batch (one %s per FurnitureBatchEnv): "
+                                          "make one FurnitureBatchEnv per furniture instead" % (f.kw, f.one))
         cfg = config if config is not None else make_config()
         for key, v in kw.items():
             setattr(cfg, key, v)

@@ -14,6 +14,7 @@ routine, which is never shallower than the true overlap and may be deeper.  The 
 import numpy as np
 
 from .camera import MAX_GEOMS
+from .rays import mask_bits
 
 MAX_SENSORS = 64         # FSIM_PAIR_MAX_SENSORS
 MAX_PAIRS = 4096         # FSIM_PAIR_MAX_PAIRS, per sensor
@@ -174,8 +175,5 @@ def sensor_table(model, pair_set):
         t = tab[i]
         t.dmax = k.dmax
         for field, mask in zip((t.a, t.b), k.side_masks(model)):
-            bits = [0, 0, 0]
-            for g in np.nonzero(mask)[0]:
-                bits[g >> 5] |= 1 << (int(g) & 31)
-            field[:] = bits
+            field[:] = mask_bits(mask)
     return tab

@@ -13,7 +13,7 @@ vertices outside.  The probes see the collision geometry the cameras and rays se
 import numpy as np
 
 from .camera import MAX_GEOMS
-from .rays import exclude_mask  # (the rule is shared; its message for an unknown geom id still says "RaySensor": to be made neutral in rays.py)
+from .rays import exclude_mask, mask_bits  # (the exclusion rule and the packing of a geom mask are shared with the ray sensors)
 
 MAX_SENSORS = 16   # FSIM_PROBE_MAX_SENSORS
 MAX_PROBES = 4096  # FSIM_PROBE_MAX_PROBES, per env over all sensors
@@ -135,12 +135,9 @@ def sensor_table(model, probe_set):
     tab = (FsimProbeSensor * len(probe_set.sensors))()
     at = 0
     for i, k in enumerate(probe_set.sensors):
-        bits = np.zeros(3, dtype=np.uint32)
-        for g in np.nonzero(exclude_mask(model, k))[0]:
-            bits[g >> 5] |= np.uint32(1) << np.uint32(g & 31)
         t = tab[i]
         t.body, t.dmax, t.first_probe, t.n_probes = k.body_id(model), k.dmax, at, k.n_probes
-        t.pos[:], t.quat[:], t.exclude[:] = k.pos.tolist(), k.quat.tolist(), [int(b) for b in bits]
+        t.pos[:], t.quat[:], t.exclude[:] = k.pos.tolist(), k.quat.tolist(), mask_bits(exclude_mask(model, k))
         at += k.n_probes
     pts = np.ascontiguousarray(np.concatenate([k.points for k in probe_set.sensors]), dtype=np.float32)
     return tab, pts

@@ -88,9 +88,17 @@ def exclude_mask(model, sensor):
     ngeom = len(A["geom_bodyid"])
     for g in sensor.exclude:
         if not 0 <= g < ngeom:
-            raise ValueError("RaySensor: exclude names geom %d (the model has %d geoms)" % (g, ngeom))
+            raise ValueError("sensor: exclude names geom %d (the model has %d geoms)" % (g, ngeom))
         mask |= cg_orig == g  # (a geom that does not collide is invisible anyway)
     return mask
+
+
+def mask_bits(mask):
+    """[3] ints: a [ncg <= 96] bool mask of colliding geoms as the 96-bit masks of the C structs hold it, bit g & 31 of word g >> 5"""
+    bits = [0, 0, 0]
+    for g in np.nonzero(mask)[0]:
+        bits[g >> 5] |= 1 << (int(g) & 31)
+    return bits
 
 
 def lidar(n_azimuth, n_elevation=1, elevation=(0.0, 0.0)):
@@ -173,12 +181,9 @@ def sensor_table(model, ray_set):
     tab = (FsimRaySensor * len(ray_set.sensors))()
     at = 0
     for i, k in enumerate(ray_set.sensors):
-        bits = np.zeros(3, dtype=np.uint32)
-        for g in np.nonzero(exclude_mask(model, k))[0]:
-            bits[g >> 5] |= np.uint32(1) << np.uint32(g & 31)
         t = tab[i]
         t.body, t.tmin, t.tmax, t.first_ray, t.n_rays = k.body_id(model), k.tmin, k.tmax, at, k.n_rays
-        t.pos[:], t.quat[:], t.exclude[:] = k.pos.tolist(), k.quat.tolist(), [int(b) for b in bits]
+        t.pos[:], t.quat[:], t.exclude[:] = k.pos.tolist(), k.quat.tolist(), mask_bits(exclude_mask(model, k))
         at += k.n_rays
     dirs = np.ascontiguousarray(np.concatenate([k.directions for k in ray_set.sensors]), dtype=np.float32)
     return tab, dirs

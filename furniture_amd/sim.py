@@ -560,10 +560,7 @@ class FSim:
         d, s = (d if depth else None), (s if segmentation else None)
         for t, dt in ((d, torch.float32), (s, torch.int32)):
             assert t is None or (tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous()), "render: out tensor of the wrong shape / type"
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_render(self._h, d.data_ptr() if d is not None else None, s.data_ptr() if s is not None else None))
-        cur.wait_stream(self.torch_stream)
+        self._sensor_call(lib().fsim_render, d.data_ptr() if d is not None else None, s.data_ptr() if s is not None else None)
         return d, s
 
     def _image_shape(self):
@@ -584,10 +581,7 @@ class FSim:
                 t = torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
             assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "%s: out[%r] of the wrong shape / type" % (name, k)
             res[k] = t
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(fn(self._h, *[res[k].data_ptr() if k in res else None for k in ("camera_depth", "camera_segmentation") + keys]))
-        cur.wait_stream(self.torch_stream)
+        self._sensor_call(fn, *self._ptrs(res, ("camera_depth", "camera_segmentation") + keys))
         return res
 
     # -- point clouds from the cameras (include/fsim_points.h, furniture_amd/points.py) ------------------------------------------
@@ -728,6 +722,46 @@ class FSim:
             raise FsimError("render_flow: no cameras set (FSim.set_cameras)")
         return self._render_derived("render_flow", lib().fsim_render_flow, ("camera_flow", "camera_velocity"), self.flow_shapes(), images, out)
 
+    # -- what the state-sensor families below share (rays, probes, pairs, frames, dynamics, contacts, wrenches) ---------------------------
+    def _set_sensors(self, fn, attr, spec, cls, install):
+        """The part the seven set_X share.  None clears the library's set (n = 0: it ignores the other arguments) and the attribute;
+        anything but a `cls` is refused; install() builds the tables and hands them to fn, and only then is the spec stored."""
+        if spec is None:
+            self._chk(fn(self._h, *[0 if t is ctypes.c_int else None for t in fn.argtypes[1:]]))
+        else:
+            if not isinstance(spec, cls):
+                raise TypeError("%s: a %s.%s, not %r" % (fn.__name__[len("fsim_"):], cls.__module__, cls.__name__, type(spec).__name__))
+            install()
+        setattr(self, attr, spec)
+
+    def _sensor_outputs(self, name, want, out):
+        """The output tensors of one sensor call.  want: {key: (shape, dtype)} as the family's X_shapes() gives it; out: None (a new tensor
+        per key) or a dict of tensors to write into, whose keys alone are computed -> {key: tensor}."""
+        torch = self.torch
+        if out is not None:
+            if not out or any(k not in want for k in out):
+                raise ValueError("%s: out holds %s (of %s)" % (name, sorted(out), sorted(want)))
+            want = {k: want[k] for k in want if k in out}
+        res = {}
+        for k, (shape, dt) in want.items():
+            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
+            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
+                raise ValueError("%s: out[%r] is not a contiguous %s tensor of shape %s on %s" % (name, k, dt, (self.n_envs,) + shape, self.device))
+            res[k] = t
+        return res
+
+    def _sensor_call(self, fn, *args):
+        """fn(handle, *args) on the handle's stream, ordered with torch's current stream both ways"""
+        cur = self.torch.cuda.current_stream(self.device)
+        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
+        self._chk(fn(self._h, *args))
+        cur.wait_stream(self.torch_stream)
+
+    @staticmethod
+    def _ptrs(res, keys):
+        """the device pointers of res's tensors in the library's argument order, None for a key that is not computed"""
+        return [res[k].data_ptr() if k in res else None for k in keys]
+
     # -- ray-cast range sensors and lidar (include/fsim_rays.h, furniture_amd/rays.py) ---------------------------------------------------
     rays = None
 
@@ -736,17 +770,13 @@ class FSim:
         Independent of the cameras: neither needs nor disturbs the other."""
         from .camera import hull_plane_table
         from .rays import RaySet, sensor_table
-        if ray_set is None:
-            self._chk(lib().fsim_set_rays(self._h, 0, None, 0, None, 0, None, None, None))
-            self.rays = None
-            return
-        if not isinstance(ray_set, RaySet):
-            raise TypeError("set_rays: a furniture_amd.rays.RaySet, not %r" % type(ray_set).__name__)
-        tab, dirs = sensor_table(self.cm, ray_set)
-        planes, adr, num = hull_plane_table(self.cm)
-        self._chk(lib().fsim_set_rays(self._h, len(tab), ctypes.addressof(tab), len(dirs), dirs.ctypes.data, len(planes),
-                                      planes.ctypes.data if len(planes) else None, adr.ctypes.data, num.ctypes.data))
-        self.rays = ray_set
+
+        def install():
+            tab, dirs = sensor_table(self.cm, ray_set)
+            planes, adr, num = hull_plane_table(self.cm)
+            self._chk(lib().fsim_set_rays(self._h, len(tab), ctypes.addressof(tab), len(dirs), dirs.ctypes.data, len(planes),
+                                          planes.ctypes.data if len(planes) else None, adr.ctypes.data, num.ctypes.data))
+        self._set_sensors(lib().fsim_set_rays, "rays", ray_set, RaySet, install)
 
     def ray_shapes(self):
         """{key: (shape, dtype)} of cast_rays' outputs (without the n_envs dimension)"""
@@ -771,23 +801,10 @@ class FSim:
         camera_segmentation, -1 = nothing hit) and, when the ray set asks for it, ray_normal (float32 [n, R, 3], the world-frame outward
         unit normal at the hit point, (0, 0, 0) = nothing hit).  out: a dict of such tensors to write into instead of new ones; a key
         that is there alone is cast alone.  Ordered with torch's current stream both ways."""
-        torch = self.torch
         if self.rays is None:
             raise FsimError("cast_rays: no rays set (FSim.set_rays)")
-        want = self.ray_shapes()
-        if out is not None:
-            if not out or any(k not in want for k in out):
-                raise ValueError("cast_rays: out holds %s (of %s)" % (sorted(out), sorted(want)))
-            want = {k: want[k] for k in want if k in out}
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            assert tuple(t.shape) == (self.n_envs,) + shape and t.dtype == dt and t.is_contiguous(), "cast_rays: out[%r] of the wrong shape / type" % k
-            res[k] = t
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_cast_rays(self._h, *[res[k].data_ptr() if k in res else None for k in ("ray_distance", "ray_geom", "ray_normal")]))
-        cur.wait_stream(self.torch_stream)
+        res = self._sensor_outputs("cast_rays", self.ray_shapes(), out)
+        self._sensor_call(lib().fsim_cast_rays, *self._ptrs(res, ("ray_distance", "ray_geom", "ray_normal")))
         return res
 
     # -- signed-distance proximity probes (include/fsim_probes.h, furniture_amd/probes.py) ------------------------------------------------
@@ -798,17 +815,13 @@ class FSim:
         library.  Independent of the cameras and the rays: needs and disturbs neither."""
         from .camera import hull_plane_table
         from .probes import ProbeSet, sensor_table
-        if probe_set is None:
-            self._chk(lib().fsim_set_probes(self._h, 0, None, 0, None, 0, None, None, None))
-            self.probes = None
-            return
-        if not isinstance(probe_set, ProbeSet):
-            raise TypeError("set_probes: a furniture_amd.probes.ProbeSet, not %r" % type(probe_set).__name__)
-        tab, pts = sensor_table(self.cm, probe_set)
-        planes, adr, num = hull_plane_table(self.cm)
-        self._chk(lib().fsim_set_probes(self._h, len(tab), ctypes.addressof(tab), len(pts), pts.ctypes.data, len(planes),
-                                        planes.ctypes.data if len(planes) else None, adr.ctypes.data, num.ctypes.data))
-        self.probes = probe_set
+
+        def install():
+            tab, pts = sensor_table(self.cm, probe_set)
+            planes, adr, num = hull_plane_table(self.cm)
+            self._chk(lib().fsim_set_probes(self._h, len(tab), ctypes.addressof(tab), len(pts), pts.ctypes.data, len(planes),
+                                            planes.ctypes.data if len(planes) else None, adr.ctypes.data, num.ctypes.data))
+        self._set_sensors(lib().fsim_set_probes, "probes", probe_set, ProbeSet, install)
 
     def probe_shapes(self):
         """{key: (shape, dtype)} of probe_distance's outputs (without the n_envs dimension)"""
@@ -828,24 +841,10 @@ class FSim:
         probe_gradient (float32 [n, P, 3], the world-frame unit gradient of the distance, (0, 0, 0) = nothing).  out: a dict of such
         tensors to write into instead of new ones; a key that is there alone is computed alone.  Ordered with torch's current stream
         both ways."""
-        torch = self.torch
         if self.probes is None:
             raise FsimError("probe_distance: no probes set (FSim.set_probes)")
-        want = self.probe_shapes()
-        if out is not None:
-            if not out or any(k not in want for k in out):
-                raise ValueError("probe_distance: out holds %s (of %s)" % (sorted(out), sorted(want)))
-            want = {k: want[k] for k in want if k in out}
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
-                raise ValueError("probe_distance: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
-            res[k] = t
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_probe_distance(self._h, *[res[k].data_ptr() if k in res else None for k in ("probe_distance", "probe_geom", "probe_gradient")]))
-        cur.wait_stream(self.torch_stream)
+        res = self._sensor_outputs("probe_distance", self.probe_shapes(), out)
+        self._sensor_call(lib().fsim_probe_distance, *self._ptrs(res, ("probe_distance", "probe_geom", "probe_gradient")))
         return res
 
     # -- geom-pair distance sensors (include/fsim_pairs.h, furniture_amd/pairs.py) ---------------------------------------------------------
@@ -855,15 +854,11 @@ class FSim:
         """Replace the handle's pair set (a furniture_amd.pairs.PairSet; None clears it); checked on the host first, then by the
         library.  Independent of the cameras, the rays and the probes: needs and disturbs none of them."""
         from .pairs import PairSet, sensor_table
-        if pair_set is None:
-            self._chk(lib().fsim_set_pairs(self._h, 0, None))
-            self.pairs = None
-            return
-        if not isinstance(pair_set, PairSet):
-            raise TypeError("set_pairs: a furniture_amd.pairs.PairSet, not %r" % type(pair_set).__name__)
-        tab = sensor_table(self.cm, pair_set)
-        self._chk(lib().fsim_set_pairs(self._h, len(tab), ctypes.addressof(tab)))
-        self.pairs = pair_set
+
+        def install():
+            tab = sensor_table(self.cm, pair_set)
+            self._chk(lib().fsim_set_pairs(self._h, len(tab), ctypes.addressof(tab)))
+        self._set_sensors(lib().fsim_set_pairs, "pairs", pair_set, PairSet, install)
 
     def pair_shapes(self):
         """{key: (shape, dtype)} of pair_distance's outputs (without the n_envs dimension)"""
@@ -885,24 +880,10 @@ class FSim:
         -1 = nothing) and, when the pair set asks for them, pair_fromto (float32 [n, S, 6], the nearest points: on side a, then on side b)
         and pair_normal (float32 [n, S, 3], the unit direction from a to b; (0, 0, 0) = nothing).  out: a dict of such tensors to write
         into instead of new ones; a key that is there alone is computed alone.  Ordered with torch's current stream both ways."""
-        torch = self.torch
         if self.pairs is None:
             raise FsimError("pair_distance: no pair set (FSim.set_pairs)")
-        want = self.pair_shapes()
-        if out is not None:
-            if not out or any(k not in want for k in out):
-                raise ValueError("pair_distance: out holds %s (of %s)" % (sorted(out), sorted(want)))
-            want = {k: want[k] for k in want if k in out}
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
-                raise ValueError("pair_distance: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
-            res[k] = t
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_pair_distance(self._h, *[res[k].data_ptr() if k in res else None for k in ("pair_distance", "pair_geoms", "pair_fromto", "pair_normal")]))
-        cur.wait_stream(self.torch_stream)
+        res = self._sensor_outputs("pair_distance", self.pair_shapes(), out)
+        self._sensor_call(lib().fsim_pair_distance, *self._ptrs(res, ("pair_distance", "pair_geoms", "pair_fromto", "pair_normal")))
         return res
 
     # -- body and site frame sensors with their Jacobians (include/fsim_frames.h, furniture_amd/frames.py) --------------------------------
@@ -912,15 +893,11 @@ class FSim:
         """Replace the handle's frame set (a furniture_amd.frames.FrameSet; None clears it); checked on the host first, then by the
         library.  Independent of the cameras, the rays, the probes and the pairs: needs and disturbs none of them."""
         from .frames import FrameSet, sensor_table
-        if frame_set is None:
-            self._chk(lib().fsim_set_frames(self._h, 0, None))
-            self.frames = None
-            return
-        if not isinstance(frame_set, FrameSet):
-            raise TypeError("set_frames: a furniture_amd.frames.FrameSet, not %r" % type(frame_set).__name__)
-        tab = sensor_table(self.cm, frame_set)
-        self._chk(lib().fsim_set_frames(self._h, len(tab), ctypes.addressof(tab)))
-        self.frames = frame_set
+
+        def install():
+            tab = sensor_table(self.cm, frame_set)
+            self._chk(lib().fsim_set_frames(self._h, len(tab), ctypes.addressof(tab)))
+        self._set_sensors(lib().fsim_set_frames, "frames", frame_set, FrameSet, install)
 
     def frame_shapes(self):
         """{key: (shape, dtype)} of frame_state's outputs (without the n_envs dimension)"""
@@ -942,24 +919,10 @@ class FSim:
         of frame_pos and the relative angular velocity, in the reference frame) and frame_jac (float32 [n, S, 6, nv], frame_vel =
         frame_jac @ qvel).  out: a dict of such tensors to write into instead of new ones; a key that is there alone is computed alone.
         Ordered with torch's current stream both ways."""
-        torch = self.torch
         if self.frames is None:
             raise FsimError("frame_state: no frame set (FSim.set_frames)")
-        want = self.frame_shapes()
-        if out is not None:
-            if not out or any(k not in want for k in out):
-                raise ValueError("frame_state: out holds %s (of %s)" % (sorted(out), sorted(want)))
-            want = {k: want[k] for k in want if k in out}
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
-                raise ValueError("frame_state: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
-            res[k] = t
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_frame_state(self._h, *[res[k].data_ptr() if k in res else None for k in ("frame_pos", "frame_quat", "frame_vel", "frame_jac")]))
-        cur.wait_stream(self.torch_stream)
+        res = self._sensor_outputs("frame_state", self.frame_shapes(), out)
+        self._sensor_call(lib().fsim_frame_state, *self._ptrs(res, ("frame_pos", "frame_quat", "frame_vel", "frame_jac")))
         return res
 
     # -- mass-matrix, inverse-inertia and bias-force tensors (include/fsim_dynamics.h, furniture_amd/dynamics.py) -------------------------
@@ -969,16 +932,12 @@ class FSim:
         """Replace the handle's dynamics selection (a furniture_amd.dynamics.Dynamics; None clears it); checked on the host first, then
         by the library.  Independent of the cameras, the rays, the probes, the pairs and the frames: needs and disturbs none of them."""
         from .dynamics import Dynamics, dof_table
-        if spec is None:
-            self._chk(lib().fsim_set_dynamics(self._h, 0, None))
-            self.dyn = None
-            return
-        if not isinstance(spec, Dynamics):
-            raise TypeError("set_dynamics: a furniture_amd.dynamics.Dynamics, not %r" % type(spec).__name__)
-        tab = dof_table(self.cm, spec)
-        self._chk(lib().fsim_set_dynamics(self._h, len(tab), tab.ctypes.data))
-        self.dyn = spec
-        self._dyn_k = len(tab)
+
+        def install():
+            tab = dof_table(self.cm, spec)
+            self._chk(lib().fsim_set_dynamics(self._h, len(tab), tab.ctypes.data))
+            self._dyn_k = len(tab)
+        self._set_sensors(lib().fsim_set_dynamics, "dyn", spec, Dynamics, install)
 
     def dynamics_shapes(self):
         """{key: (shape, dtype)} of dynamics' outputs (without the n_envs dimension)"""
@@ -995,24 +954,10 @@ class FSim:
         restricted to dofs), dyn_bias (float32 [n, K], qfrc_bias[dofs]) and dyn_gravity (float32 [n, K], the same at qvel = 0).  out: a
         dict of such tensors to write into instead of new ones; a key that is there alone is computed alone.  Ordered with torch's
         current stream both ways."""
-        torch = self.torch
         if self.dyn is None:
             raise FsimError("dynamics: no dof selection (FSim.set_dynamics)")
-        want = self.dynamics_shapes()
-        if out is not None:
-            if not out or any(k not in want for k in out):
-                raise ValueError("dynamics: out holds %s (of %s)" % (sorted(out), sorted(want)))
-            want = {k: want[k] for k in want if k in out}
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
-                raise ValueError("dynamics: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
-            res[k] = t
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_dynamics(self._h, *[res[k].data_ptr() if k in res else None for k in ("dyn_mass", "dyn_minv", "dyn_bias", "dyn_gravity")]))
-        cur.wait_stream(self.torch_stream)
+        res = self._sensor_outputs("dynamics", self.dynamics_shapes(), out)
+        self._sensor_call(lib().fsim_dynamics, *self._ptrs(res, ("dyn_mass", "dyn_minv", "dyn_bias", "dyn_gravity")))
         return res
 
     # -- contact-force and touch sensors (include/fsim_contacts.h, furniture_amd/contacts.py) -------------------------------------------
@@ -1022,17 +967,13 @@ class FSim:
         """Replace the handle's contact sensors (a furniture_amd.contacts.ContactSet; None clears them); checked on the host first, then
         by the library.  Independent of the cameras, the rays, the probes, the pairs, the frames and the dynamics tensors."""
         from .contacts import MAX_SLOTS, ContactSet, sensor_table
-        if contact_set is None:
-            self._chk(lib().fsim_set_contacts(self._h, 0, None))
-            self.contacts = None
-            return
-        if not isinstance(contact_set, ContactSet):
-            raise TypeError("set_contacts: a furniture_amd.contacts.ContactSet, not %r" % type(contact_set).__name__)
-        if self.max_contacts > MAX_SLOTS:
-            raise ValueError("contacts: the handle has %d contact slots (the contact-force pass serves at most %d)" % (self.max_contacts, MAX_SLOTS))
-        tab = sensor_table(self.cm, contact_set)
-        self._chk(lib().fsim_set_contacts(self._h, len(tab), ctypes.cast(tab, ctypes.c_void_p)))
-        self.contacts = contact_set
+
+        def install():
+            if self.max_contacts > MAX_SLOTS:
+                raise ValueError("contacts: the handle has %d contact slots (the contact-force pass serves at most %d)" % (self.max_contacts, MAX_SLOTS))
+            tab = sensor_table(self.cm, contact_set)
+            self._chk(lib().fsim_set_contacts(self._h, len(tab), ctypes.cast(tab, ctypes.c_void_p)))
+        self._set_sensors(lib().fsim_set_contacts, "contacts", contact_set, ContactSet, install)
 
     def contact_shapes(self):
         """{key: (shape, dtype)} of contact_forces' outputs (without the n_envs dimension)"""
@@ -1051,28 +992,11 @@ class FSim:
         to be trusted) and, with the set's contacts=True, con_geoms (int32 [n, C, 2]), con_pos, con_normal, con_force (float32 [n, C, 3]),
         con_dist and con_fn (float32 [n, C]).  out: a dict of such tensors to write into instead of new ones; a key that is there alone
         is computed alone.  Reads the env records and writes nothing else.  Ordered with torch's current stream both ways."""
-        torch = self.torch
         if self.contacts is None:
             raise FsimError("contact_forces: no sensor set (FSim.set_contacts)")
-        want = self.contact_shapes()
-        if out is not None:
-            if not out or any(k not in want for k in out):
-                raise ValueError("contact_forces: out holds %s (of %s)" % (sorted(out), sorted(want)))
-            want = {k: want[k] for k in want if k in out}
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
-                raise ValueError("contact_forces: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
-            res[k] = t
-        ptrs = FsimContactOut()
-        for field in CONTACT_OUT_FIELDS:
-            key = field if field.startswith("con_") else "contact_" + field
-            setattr(ptrs, field, res[key].data_ptr() if key in res else None)
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_contact_forces(self._h, ctypes.byref(ptrs)))
-        cur.wait_stream(self.torch_stream)
+        res = self._sensor_outputs("contact_forces", self.contact_shapes(), out)
+        keys = [f if f.startswith("con_") else "contact_" + f for f in CONTACT_OUT_FIELDS]
+        self._sensor_call(lib().fsim_contact_forces, ctypes.byref(FsimContactOut(*self._ptrs(res, keys))))
         return res
 
     # -- force-torque, accelerometer and joint-load sensors (include/fsim_wrench.h, furniture_amd/wrench.py) ------------------------------
@@ -1082,17 +1006,13 @@ class FSim:
         """Replace the handle's wrench sensors (a furniture_amd.wrench.WrenchSet; None clears them); checked on the host first, then by the
         library.  Independent of every other sensor family."""
         from .wrench import MAX_SLOTS, WrenchSet, sensor_table
-        if wrench_set is None:
-            self._chk(lib().fsim_set_wrenches(self._h, 0, None))
-            self.wrench_set = None
-            return
-        if not isinstance(wrench_set, WrenchSet):
-            raise TypeError("set_wrenches: a furniture_amd.wrench.WrenchSet, not %r" % type(wrench_set).__name__)
-        if self.max_contacts > MAX_SLOTS:
-            raise ValueError("wrenches: the handle has %d contact slots (the wrench pass serves at most %d)" % (self.max_contacts, MAX_SLOTS))
-        tab = sensor_table(self.cm, wrench_set)
-        self._chk(lib().fsim_set_wrenches(self._h, len(tab), ctypes.cast(tab, ctypes.c_void_p)))
-        self.wrench_set = wrench_set
+
+        def install():
+            if self.max_contacts > MAX_SLOTS:
+                raise ValueError("wrenches: the handle has %d contact slots (the wrench pass serves at most %d)" % (self.max_contacts, MAX_SLOTS))
+            tab = sensor_table(self.cm, wrench_set)
+            self._chk(lib().fsim_set_wrenches(self._h, len(tab), ctypes.cast(tab, ctypes.c_void_p)))
+        self._set_sensors(lib().fsim_set_wrenches, "wrench_set", wrench_set, WrenchSet, install)
 
     def wrench_shapes(self):
         """{key: (shape, dtype)} of wrenches' outputs (without the n_envs dimension)"""
@@ -1110,27 +1030,10 @@ class FSim:
         external=True, wrench_external (float32 [n, S, 6], world frame), with joint=True wrench_qacc and wrench_qfrc_constraint (float32
         [n, nv]).  out: a dict of such tensors to write into instead of new ones; a key that is there alone is computed alone.  Reads the
         env records and writes nothing else.  Ordered with torch's current stream both ways."""
-        torch = self.torch
         if self.wrench_set is None:
             raise FsimError("wrenches: no sensor set (FSim.set_wrenches)")
-        want = self.wrench_shapes()
-        if out is not None:
-            if not out or any(k not in want for k in out):
-                raise ValueError("wrenches: out holds %s (of %s)" % (sorted(out), sorted(want)))
-            want = {k: want[k] for k in want if k in out}
-        res = {}
-        for k, (shape, dt) in want.items():
-            t = out[k] if out is not None else torch.empty((self.n_envs,) + shape, dtype=dt, device=self.device)
-            if tuple(t.shape) != (self.n_envs,) + shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:  # (a raw pointer goes to the kernel)
-                raise ValueError("wrenches: out[%r] is not a contiguous %s tensor of shape %s on %s" % (k, dt, (self.n_envs,) + shape, self.device))
-            res[k] = t
-        ptrs = FsimWrenchOut()
-        for field in WRENCH_OUT_FIELDS:
-            setattr(ptrs, field, res["wrench_" + field].data_ptr() if "wrench_" + field in res else None)
-        cur = torch.cuda.current_stream(self.device)
-        self.torch_stream.wait_stream(cur)  # (the outputs may be memory torch's stream has just released)
-        self._chk(lib().fsim_wrenches(self._h, ctypes.byref(ptrs)))
-        cur.wait_stream(self.torch_stream)
+        res = self._sensor_outputs("wrenches", self.wrench_shapes(), out)
+        self._sensor_call(lib().fsim_wrenches, ctypes.byref(FsimWrenchOut(*self._ptrs(res, ["wrench_" + f for f in WRENCH_OUT_FIELDS]))))
         return res
 
     def kernel_time_ms(self):

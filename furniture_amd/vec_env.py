@@ -8,7 +8,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .envs import GYM_IDS, REGISTRY, FurnitureBatchEnv, make_config
+from .envs import GYM_IDS, REGISTRY, SENSOR_FAMILIES, FurnitureBatchEnv, make_config
 from .sim import INFO_EPISODE_REWARD_F
 
 
@@ -57,27 +57,10 @@ class FurnitureVecEnv:
         if kw.pop("flow", None) is not None:
             raise NotImplementedError("flow= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., cameras=[...], flow=Flow(...)), whose images stay on the device")
-        if kw.pop("rays", None) is not None:
-            raise NotImplementedError("rays= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
-                                      "FurnitureBatchEnv(..., rays=RaySet(...)), whose ray outputs stay on the device")
-        if kw.pop("probes", None) is not None:
-            raise NotImplementedError("probes= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
-                                      "FurnitureBatchEnv(..., probes=ProbeSet(...)), whose probe outputs stay on the device")
-        if kw.pop("pairs", None) is not None:
-            raise NotImplementedError("pairs= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
-                                      "FurnitureBatchEnv(..., pairs=PairSet(...)), whose pair outputs stay on the device")
-        if kw.pop("frames", None) is not None:
-            raise NotImplementedError("frames= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
-                                      "FurnitureBatchEnv(..., frames=FrameSet(...)), whose frame outputs stay on the device")
-        if kw.pop("dynamics", None) is not None:
-            raise NotImplementedError("dynamics= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
-                                      "FurnitureBatchEnv(..., dynamics=Dynamics(...)), whose dynamics outputs stay on the device")
-        if kw.pop("contacts", None) is not None:
-            raise NotImplementedError("contacts= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
-                                      "FurnitureBatchEnv(..., contacts=ContactSet(...)), whose contact outputs stay on the device")
-        if kw.pop("wrenches", None) is not None:
-            raise NotImplementedError("wrenches= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
-                                      "FurnitureBatchEnv(..., wrenches=WrenchSet(...)), whose wrench outputs stay on the device")
+        for f in SENSOR_FAMILIES:
+            if kw.pop(f.kw, None) is not None:
+                raise NotImplementedError("%s= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
+                                          "FurnitureBatchEnv(..., %s=%s(...)), whose %s outputs stay on the device" % (f.kw, f.kw, f.cls, f.noun))
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]

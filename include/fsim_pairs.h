@@ -73,7 +73,7 @@ typedef struct fsim_pair_sensor {
  * pointer, copied before return; the call waits for the handle's stream before it replaces the tables.  FSIM_EINVAL, each with a message:
  * more than 64 sensors, more than 4096 pairs in a sensor or 16384 over the set, a side without a geom, a sensor with no valid pair (every
  * (g1, g2) has g1 == g2 or two planes), a mask bit at or beyond the number of colliding geoms, a dmax that is not 0 < dmax < inf, a model
- * with more than 96 colliding geoms. */
+ * with more than 96 colliding geoms.  A refused call leaves the previous set in place. */
 int fsim_set_pairs(fsim_t *, int n_sensors, const fsim_pair_sensor_t *sensors);
 
 /* The distance of every sensor of every env: dist_dev float32 [n_envs][S], geoms_dev int32 [n_envs][S][2], fromto_dev float32

@@ -68,7 +68,8 @@ typedef struct fsim_probe_sensor {
  * handle's stream before it replaces the tables.  FSIM_EINVAL, each with a message: more than 16 sensors, no or more than 4096 probes, a
  * sensor without a probe, slices that are not contiguous or do not cover the table, a body unknown to the model, a pose that is not
  * finite, a dmax that is not 0 < dmax < inf, an exclude bit at or beyond the number of colliding geoms, a non-finite point, more than 96
- * colliding geoms or 1024 hull planes (the caps of fsim_camera.h), a mesh collider without planes. */
+ * colliding geoms or 1024 hull planes (the caps of fsim_camera.h), a mesh collider without planes.
+ * A refused call leaves the previous set in place. */
 int fsim_set_probes(fsim_t *, int n_sensors, const fsim_probe_sensor_t *sensors, int n_probes, const float *pts, int n_planes,
                     const float *hull_planes, const int32_t *hull_adr, const int32_t *hull_num);
 

@@ -53,7 +53,8 @@ typedef struct fsim_ray_sensor {
  * waits for the handle's stream before it replaces the tables.  FSIM_EINVAL, each with a message: more than 16 sensors, no or more than
  * 4096 rays, a sensor without a ray, slices that are not contiguous or do not cover the table, a body unknown to the model, a pose that is
  * not finite, a range that is not 0 <= tmin < tmax < inf, an exclude bit at or beyond the number of colliding geoms, a zero or
- * non-finite direction, more than 96 colliding geoms or 1024 hull planes (the caps of fsim_camera.h), a mesh collider without planes. */
+ * non-finite direction, more than 96 colliding geoms or 1024 hull planes (the caps of fsim_camera.h), a mesh collider without planes.
+ * A refused call leaves the previous set in place. */
 int fsim_set_rays(fsim_t *, int n_sensors, const fsim_ray_sensor_t *sensors, int n_rays, const float *dirs, int n_planes,
                   const float *hull_planes, const int32_t *hull_adr, const int32_t *hull_num);
 

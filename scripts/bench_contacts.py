@@ -8,51 +8,19 @@ import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
+import bench_common
 from furniture_amd.contacts import ContactSensor, ContactSet, part_sensors
 from furniture_amd.dynamics import Dynamics
-from furniture_amd.envs import ResetTableSampler, make_config
 from furniture_amd.frames import Frame, FrameSensor, FrameSet
-from furniture_amd.mjcf.model import load_compiled
-from furniture_amd.sim import INFO_DIM, FSim, default_config
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 
-furniture = "table_lack_0825"
-m = load_compiled("Sawyer", furniture)
-ecfg = make_config(unity=False, record_vid=False, furniture_name=furniture, seed=7)
-cfg = default_config()
-cfg.auto_reset = 0
-sim = FSim(m, n, config=cfg)
-p, nz = ResetTableSampler(m, ecfg, 7, 0, n).draw()
-sim.set_reset_tables(p, nz)
-dev = sim.device
-obs, rew = torch.zeros((n, sim.obs_dim), device=dev), torch.zeros(n, device=dev)
-done, info = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros((n, INFO_DIM), dtype=torch.int32, device=dev)
-sim.reset(None, obs)
-sim.sync()
-rng = np.random.RandomState(0)
-for _ in range(3):
-    act = torch.as_tensor(rng.uniform(-1, 1, (n, sim.dof_action)).astype(np.float32), device=dev)
-    torch.cuda.synchronize()
-    sim.step(act, obs, rew, done, info)
-    sim.sync()
+m, sim = bench_common.make("Sawyer", "table_lack_0825", n)
 
 
 def median_ms(fn):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    with torch.cuda.stream(sim.torch_stream):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    return float(np.median(ms))
+    return bench_common.median_ms(sim, fn, reps, warmup=5)
 
 
 def report(name, t, out, **kw):

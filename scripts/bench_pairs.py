@@ -8,56 +8,19 @@ import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from furniture_amd.envs import ResetTableSampler, make_config
-from furniture_amd.mjcf.model import load_compiled
+import bench_common
 from furniture_amd.pairs import PairSensor, PairSet, gripper_bodies
 from furniture_amd.probes import ProbeSensor, ProbeSet
-from furniture_amd.sim import INFO_DIM, FSim, default_config
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 
 
-def make(furniture):
-    """a handle of n envs of Sawyer + furniture after a reset and three random steps"""
-    m = load_compiled("Sawyer", furniture)
-    ecfg = make_config(unity=False, record_vid=False, furniture_name=furniture, seed=7)
-    cfg = default_config()
-    cfg.auto_reset = 0
-    sim = FSim(m, n, config=cfg)
-    p, nz = ResetTableSampler(m, ecfg, 7, 0, n).draw()
-    sim.set_reset_tables(p, nz)
-    dev = sim.device
-    obs, rew = torch.zeros((n, sim.obs_dim), device=dev), torch.zeros(n, device=dev)
-    done, info = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros((n, INFO_DIM), dtype=torch.int32, device=dev)
-    sim.reset(None, obs)
-    sim.sync()
-    rng = np.random.RandomState(0)
-    for _ in range(3):
-        act = torch.as_tensor(rng.uniform(-1, 1, (n, sim.dof_action)).astype(np.float32), device=dev)
-        torch.cuda.synchronize()
-        sim.step(act, obs, rew, done, info)
-        sim.sync()
-    return m, sim
-
-
-m, sim = make("table_lack_0825")
+m, sim = bench_common.make("Sawyer", "table_lack_0825", n)
 
 
 def median_ms(fn):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    with torch.cuda.stream(sim.torch_stream):
-        for _ in range(reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-    return float(np.median(ms))
+    return bench_common.median_ms(sim, fn, reps)
 
 
 def parts(m):
@@ -102,7 +65,7 @@ run("", m, {"gripper_to_5_parts": [PairSensor(G, p, dmax=3.0) for p in P], "arm_
             "all_part_pairs": [PairSensor(P[i], P[j], dmax=3.0) for i in range(len(P)) for j in range(i + 1, len(P))]})
 sim.close()
 # a model with a hull collider: chair_agne_0010's seat (433 hull vertices: every support evaluation walks them)
-m, sim = make("chair_agne_0010")
+m, sim = bench_common.make("Sawyer", "chair_agne_0010", n)
 hull = [int(g) for g in np.asarray(m.arrays["cg_orig"]) if int(m.arrays["geom_type"][int(g)]) == 7][0]
 run("chair_", m, {"gripper_to_hull": [PairSensor(gripper_bodies(m), [hull], dmax=3.0)]})
 sim.close()

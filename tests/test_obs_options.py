@@ -107,3 +107,64 @@ def test_argparse_intake_has_the_reference_option_names():
         assert d.max_episode_steps == 150 and d.control_type == "impedance" and d.phase_bonus == 5000.0 and d.phase_ob is False
     finally:
         sys.argv = argv
+
+
+# ---- the state-sensor families are refused by the wrappers that cannot carry them, each in its own words ------------------------------
+SENSOR_REFUSALS = [  # (keyword, FSim attribute, VecEnv wrapper, mixed batch, multi-GPU gather): the messages written out, not built from the table
+    ("rays", "rays",
+     "rays= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use FurnitureBatchEnv(..., rays=RaySet(...)), whose ray outputs stay on the device",
+     "rays= is not supported by the mixed-furniture batch (one ray set per FurnitureBatchEnv): make one FurnitureBatchEnv per furniture instead",
+     "step_wait_and_gather: ray-sensor outputs are not part of the multi-GPU gather; cast them on each rank instead"),
+    ("probes", "probes",
+     "probes= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use FurnitureBatchEnv(..., probes=ProbeSet(...)), whose probe outputs stay on the device",
+     "probes= is not supported by the mixed-furniture batch (one probe set per FurnitureBatchEnv): make one FurnitureBatchEnv per furniture instead",
+     "step_wait_and_gather: distance-probe outputs are not part of the multi-GPU gather; compute them on each rank instead"),
+    ("pairs", "pairs",
+     "pairs= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use FurnitureBatchEnv(..., pairs=PairSet(...)), whose pair outputs stay on the device",
+     "pairs= is not supported by the mixed-furniture batch (one pair set per FurnitureBatchEnv): make one FurnitureBatchEnv per furniture instead",
+     "step_wait_and_gather: pair-distance outputs are not part of the multi-GPU gather; compute them on each rank instead"),
+    ("frames", "frames",
+     "frames= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use FurnitureBatchEnv(..., frames=FrameSet(...)), whose frame outputs stay on the device",
+     "frames= is not supported by the mixed-furniture batch (one frame set per FurnitureBatchEnv): make one FurnitureBatchEnv per furniture instead",
+     "step_wait_and_gather: frame-sensor outputs are not part of the multi-GPU gather; compute them on each rank instead"),
+    ("dynamics", "dyn",
+     "dynamics= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use FurnitureBatchEnv(..., dynamics=Dynamics(...)), whose dynamics outputs stay on the device",
+     "dynamics= is not supported by the mixed-furniture batch (one dof selection per FurnitureBatchEnv): make one FurnitureBatchEnv per furniture instead",
+     "step_wait_and_gather: dynamics tensors are not part of the multi-GPU gather; compute them on each rank instead"),
+    ("contacts", "contacts",
+     "contacts= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use FurnitureBatchEnv(..., contacts=ContactSet(...)), whose contact outputs stay on the device",
+     "contacts= is not supported by the mixed-furniture batch (one contact set per FurnitureBatchEnv): make one FurnitureBatchEnv per furniture instead",
+     "step_wait_and_gather: contact-force outputs are not part of the multi-GPU gather; compute them on each rank instead"),
+    ("wrenches", "wrench_set",
+     "wrenches= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use FurnitureBatchEnv(..., wrenches=WrenchSet(...)), whose wrench outputs stay on the device",
+     "wrenches= is not supported by the mixed-furniture batch (one wrench set per FurnitureBatchEnv): make one FurnitureBatchEnv per furniture instead",
+     "step_wait_and_gather: wrench-sensor outputs are not part of the multi-GPU gather; compute them on each rank instead"),
+]
+
+
+def test_the_refusal_table_covers_every_family():
+    from furniture_amd.envs import SENSOR_FAMILIES
+    assert [(f.kw, f.attr) for f in SENSOR_FAMILIES] == [(r[0], r[1]) for r in SENSOR_REFUSALS]
+
+
+@pytest.mark.parametrize("kw,attr,vec_msg,mixed_msg,gather_msg", SENSOR_REFUSALS, ids=[r[0] for r in SENSOR_REFUSALS])
+def test_sensor_families_are_refused_in_the_parents_words(kw, attr, vec_msg, mixed_msg, gather_msg):
+    from furniture_amd.dist import step_wait_and_gather
+    from furniture_amd.mixed import FurnitureMixedBatchEnv
+    from furniture_amd.vec_env import FurnitureVecEnv
+    spec = object()  # (refused for being there, before anything looks at it)
+    with pytest.raises(NotImplementedError) as e:
+        FurnitureVecEnv("FurnitureSawyerEnv", 2, env_kwargs={kw: spec})
+    assert str(e.value) == vec_msg
+    with pytest.raises(NotImplementedError) as e:
+        FurnitureMixedBatchEnv("Sawyer", ["table_lack_0825", "chair_agne_0010"], 4, **{kw: spec})
+    assert str(e.value) == mixed_msg
+
+    class _Handle:  # a handle with this family's set and nothing else
+        def sync(self):
+            raise AssertionError("refused before the sync")
+    handle = _Handle()
+    setattr(handle, attr, spec)
+    with pytest.raises(NotImplementedError) as e:
+        step_wait_and_gather(handle, None, None, None)
+    assert str(e.value) == gather_msg
