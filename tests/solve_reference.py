@@ -29,6 +29,7 @@ The measures (all through the float64 mass matrix M, so that they are forces):
           worst island of the env.  Trees that no constraint touches are not islands of the solve and are left to `force`.
   step    (qvel after one substep - qvel) / h against the oracle's, through M, on the scale of `force`: the damped integrator's own
           fs_chol_solve call on top of the solve"""
+import contextlib
 import ctypes
 import os
 
@@ -101,19 +102,19 @@ FLOOR = {
 _models = {}
 
 
-def model(case):
+def model(case, cases=None):
     from furniture_amd.mjcf.model import load_compiled
-    key = CASES[case]["model"]
+    key = (cases or CASES)[case]["model"]
     if key not in _models:
         _models[key] = load_compiled(*key)
     return _models[key]
 
 
-def load(path=GOLDEN):
-    """name -> dict(st: state dict of [n, .] arrays, island: [n] the largest island of each env)"""
+def load(path=GOLDEN, cases=None):
+    """name -> dict(st: state dict of [n, .] arrays, island: [n] the largest island of each env) of the cases (default: CASES) stored at path"""
     out = {}
     with np.load(path) as z:
-        for name in CASES:
+        for name in (cases or CASES):
             st = {k: (z["%s/%s" % (name, k)].astype(np.int32) if k in INT_FIELDS else z["%s/%s" % (name, k)].astype(np.float64)) for k in FIELDS}
             st["cursor"] = None
             out[name] = dict(st=st, island=z["%s/island" % name].astype(np.int64))
@@ -233,9 +234,9 @@ def pair_key(g1, g2):
     return (int(min(g1, g2)), int(max(g1, g2)))
 
 
-def conditions(m, case, st, e, ref, pairs32):
+def conditions(m, case, st, e, ref, pairs32, cases=None):
     """the problems of env e as a list of strings (empty: the state is usable).  ref: reference() at the state, pairs32: the contact pairs
-    the checker's float32 build lists there.
+    the checker's float32 build lists there, cases: the table that holds `case` (default: CASES).
     Threshold-free: both builds list the same pairs; no float64 contact distance within CONTACT_BAND of the pair's margin; no limited joint
     within LIMIT_ULPS float32 spacings of the threshold of its limit.  The one exception: what sits EXACTLY on a threshold -- a pair of two robot geoms whose float64
     distance is the margin to 1e-9 m or that only the float32 build lists (Sawyer's l0 sphere on the base cylinder, distance 0: it carries no
@@ -263,12 +264,13 @@ def conditions(m, case, st, e, ref, pairs32):
         for dist, end in ((q[j] - rg[j, 0], rg[j, 0]), (rg[j, 1] - q[j], rg[j, 1])):
             if abs(dist - mg[j]) <= LIMIT_ULPS * np.spacing(np.float32(abs(end))) and not (mg[j] == 0 and np.float32(q[j]) == np.float32(end)):
                 bad.append("joint at qpos[%d] is %.3e from the threshold of its limit" % (qa[j], dist - mg[j]))
-    want = CASES[case]["island"]
+    cases = cases or CASES
+    want = cases[case]["island"]
     size = island_dofs(m, ref["contacts"], st["eq_active"][e])[0]
     if want is not None and size not in want:
         bad.append("the largest island has %d dofs, the case wants %s" % (size, want))
-    if len(ref["contacts"]) > CASES[case]["slots"] or len(pairs32) > CASES[case]["slots"]:
-        bad.append("%d contacts do not fit %d slots" % (max(len(ref["contacts"]), len(pairs32)), CASES[case]["slots"]))
+    if len(ref["contacts"]) > cases[case]["slots"] or len(pairs32) > cases[case]["slots"]:
+        bad.append("%d contacts do not fit %d slots" % (max(len(ref["contacts"]), len(pairs32)), cases[case]["slots"]))
     return bad
 
 
@@ -295,3 +297,57 @@ def abi_solve(path, m, st, warm):
     qvel = ses.get_state(m, "qvel")["qvel"].astype(np.float64)
     ses.close()
     return buf.astype(np.float64), (qvel - st["qvel"]) / float(m.arrays["opt"][0]), pairs
+
+
+# ---- the kernel sets of the device ----------------------------------------------------------------------------------------------------------
+ENV_VARS = ("FSIM_MW", "FSIM_GENERIC", "FSIM_NCON_MAX")
+# kernel set -> model, the environment fsim_create reads, the variant the handle must report and its contact slots
+KSETS = {
+    "spec-mw0": dict(model=LACK, env=dict(FSIM_MW="0"), variant="sawyer_table_lack_0825", slots=48),
+    "spec-mwall": dict(model=LACK, env=dict(FSIM_MW="all"), variant="sawyer_table_lack_0825", slots=48),
+    "generic-mw0": dict(model=LACK, env=dict(FSIM_MW="0", FSIM_GENERIC="1"), variant="generic", slots=48),
+    "generic-mwall": dict(model=LACK, env=dict(FSIM_MW="all", FSIM_GENERIC="1"), variant="generic", slots=48),
+    "generic2": dict(model=LACK, env=dict(FSIM_MW="0", FSIM_NCON_MAX="128"), variant="generic2", slots=128),
+    "generic8": dict(model=LACK, env=dict(FSIM_MW="0", FSIM_NCON_MAX="512"), variant="generic8", slots=512),
+    "billy-generic2": dict(model=BILLY, env=dict(FSIM_MW="0"), variant="generic2", slots=128),
+    "billy-generic8": dict(model=BILLY, env=dict(FSIM_MW="0", FSIM_NCON_MAX="512"), variant="generic8", slots=512),
+    "desk-mw0": dict(model=DESK, env=dict(FSIM_MW="0"), variant="generic", slots=64),
+    "desk-mwall": dict(model=DESK, env=dict(FSIM_MW="all"), variant="generic", slots=64),
+}
+
+
+@contextlib.contextmanager
+def environment(env):
+    """the variables fsim_create reads, set for the creation of a handle and restored (as test_specialised_and_generic_kernels_agree does)"""
+    saved = {k: os.environ.get(k) for k in ENV_VARS}
+    for k in ENV_VARS:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def handle(cache, ks, n=MAX_ENVS):
+    """the handle of a kernel set and its twin, n envs each, made once per cache (a dict that the caller closes with close_handles)"""
+    if ks not in cache:
+        from furniture_amd.mjcf.model import load_compiled
+        from furniture_amd.sim import FSim
+        k = KSETS[ks]
+        with environment(k["env"]):
+            cache[ks] = (FSim(load_compiled(*k["model"]), n), FSim(load_compiled(*k["model"]), n))
+        for sim in cache[ks]:
+            assert sim.kernel_variant == k["variant"] and sim.max_contacts == k["slots"], (ks, sim.kernel_variant, sim.max_contacts)
+    return cache[ks]
+
+
+def close_handles(cache):
+    for pair in cache.values():
+        for sim in pair:
+            sim.close()
+    cache.clear()

@@ -14,13 +14,10 @@ with each other.
 The tolerance of a measure is 4 x the largest value measured on an MI355X for the case (the rule of DESIGN.md 15; the values:
 DESIGN.md 4).  One condition is not a measurement: a measured value above 10 x the case's fp32 floor (sref.FLOOR: what the checker's float32
 build does to the same measure) would be a defect to find, not a tolerance to widen.  Every test prints its figures before it asserts."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
-from furniture_amd.sim import FSim, default_config
+from furniture_amd.sim import default_config
 from oracle import oracle_sim
 from oracle.oracle_sim import OracleSim
 from tests import solve_reference as sref
@@ -47,49 +44,16 @@ MEASURED = {
 TOL = {g: {k: 4.0 * v for k, v in d.items()} for g, d in MEASURED.items()}
 ITER_SLACK = 3  # (the bound of tests/test_overflow_restep_gpu.py)
 N = sref.MAX_ENVS
-ENV_VARS = ("FSIM_MW", "FSIM_GENERIC", "FSIM_NCON_MAX")
-# kernel set -> model, the environment fsim_create reads, the variant the handle must report and its contact slots
-KSETS = {
-    "spec-mw0": dict(model=sref.LACK, env=dict(FSIM_MW="0"), variant="sawyer_table_lack_0825", slots=48),
-    "spec-mwall": dict(model=sref.LACK, env=dict(FSIM_MW="all"), variant="sawyer_table_lack_0825", slots=48),
-    "generic-mw0": dict(model=sref.LACK, env=dict(FSIM_MW="0", FSIM_GENERIC="1"), variant="generic", slots=48),
-    "generic-mwall": dict(model=sref.LACK, env=dict(FSIM_MW="all", FSIM_GENERIC="1"), variant="generic", slots=48),
-    "generic2": dict(model=sref.LACK, env=dict(FSIM_MW="0", FSIM_NCON_MAX="128"), variant="generic2", slots=128),
-    "generic8": dict(model=sref.LACK, env=dict(FSIM_MW="0", FSIM_NCON_MAX="512"), variant="generic8", slots=512),
-    "billy-generic2": dict(model=sref.BILLY, env=dict(FSIM_MW="0"), variant="generic2", slots=128),
-    "billy-generic8": dict(model=sref.BILLY, env=dict(FSIM_MW="0", FSIM_NCON_MAX="512"), variant="generic8", slots=512),
-    "desk-mw0": dict(model=sref.DESK, env=dict(FSIM_MW="0"), variant="generic", slots=64),
-    "desk-mwall": dict(model=sref.DESK, env=dict(FSIM_MW="all"), variant="generic", slots=64),
-}
+KSETS, _environment = sref.KSETS, sref.environment
 # every case on every kernel set of its model that holds it: pile11's island of 66 dofs needs the kernel with 512 slots (fs_chol_all_lds)
 RUNS = [(name, ks) for name, c in sref.CASES.items() for ks, k in KSETS.items() if k["model"] == c["model"] and not (name == "pile11" and ks == "billy-generic2")]
 _handles, _runs, _refs = {}, {}, {}
 
 
-@contextlib.contextmanager
-def _environment(env):
-    """the variables fsim_create reads, set for the creation of a handle and restored (as test_specialised_and_generic_kernels_agree does)"""
-    saved = {k: os.environ.get(k) for k in ENV_VARS}
-    for k in ENV_VARS:
-        os.environ.pop(k, None)
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 @pytest.fixture(scope="module", autouse=True)
 def _close_handles():
     yield
-    for pair in _handles.values():
-        for sim in pair:
-            sim.close()
-    _handles.clear()
+    sref.close_handles(_handles)
 
 
 @pytest.fixture(scope="module")
@@ -99,14 +63,7 @@ def stored():
 
 def _handle(ks):
     """the handle of a kernel set and its twin: N envs each, made once"""
-    if ks not in _handles:
-        k = KSETS[ks]
-        from furniture_amd.mjcf.model import load_compiled
-        with _environment(k["env"]):
-            _handles[ks] = (FSim(load_compiled(*k["model"]), N), FSim(load_compiled(*k["model"]), N))
-        for sim in _handles[ks]:
-            assert sim.kernel_variant == k["variant"] and sim.max_contacts == k["slots"], (ks, sim.kernel_variant, sim.max_contacts)
-    return _handles[ks]
+    return sref.handle(_handles, ks, N)
 
 
 def _reference(name, stored, warm):
