@@ -517,6 +517,7 @@ struct FrameState; // fsim_frames.hpp
 struct DynState; // fsim_dynamics.hpp
 struct ConState; // fsim_contacts.hpp
 struct WrState; // fsim_wrench.hpp
+struct MomState; // fsim_momentum.hpp
 struct KernelSet { const char *name; PhysicsFn physics; EnvStepFn env_step; PhysicsFn physics_mw; EnvStepFn env_step_mw; EnvStepXFn env_step_x; };
 enum { MW_OFF = 0, MW_RULE = 1, MW_ALL = 2 }; // fsim::mw_mode
 
@@ -606,6 +607,7 @@ struct fsim {
   DynState *dyn = nullptr; // mass matrix, inverse inertia and bias forces: the dof selection (fsim_set_dynamics): nothing is allocated or launched without it
   ConState *con = nullptr; // contact-force and touch sensors: the sensor table (fsim_set_contacts): nothing is allocated or launched without it
   WrState *wr = nullptr; // force-torque, accelerometer and joint-load sensors: the sensor table (fsim_set_wrenches): nothing is allocated or launched without it
+  MomState *mom = nullptr; // centre-of-mass, momentum and energy sensors: the body masks (fsim_set_momenta): nothing is allocated or launched without them
 };
 
 static void la_policy(fsim *s);
@@ -1047,7 +1049,7 @@ extern "C" int fsim_sync(fsim_t *s) {
   return settle(s);
 }
 
-// ---- what the state-sensor families (rays, probes, pairs, frames, dynamics, contacts, wrenches) share on the host
+// ---- what the state-sensor families (rays, probes, pairs, frames, dynamics, contacts, wrenches, momenta) share on the host
 // The device tables of one sensor state.  The state keeps its typed pointers for the kernels' arguments; this owns what they point to:
 // put() allocates and uploads and, after the first error, does nothing more; release() frees everything put() allocated.
 struct DevTables {
@@ -1719,6 +1721,7 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
 #include "fsim_dynamics.hpp"
 #include "fsim_contacts.hpp"
 #include "fsim_wrench.hpp"
+#include "fsim_momentum.hpp"
 
 // (below the sensor files: it frees their states, which are complete types only here)
 extern "C" void fsim_destroy(fsim_t *s) {
@@ -1737,6 +1740,7 @@ extern "C" void fsim_destroy(fsim_t *s) {
   sensor_free(s->dyn);
   sensor_free(s->con);
   sensor_free(s->wr);
+  sensor_free(s->mom);
   hipFree(s->d_sh_state); hipFree(s->d_sh_obs); hipFree(s->d_sh_prog); hipFree(s->d_sh_serial); hipFree(s->d_tab_serial); hipFree(s->d_sh_jobs);
   if (s->xfer) { hipStreamSynchronize(s->xfer); hipStreamDestroy(s->xfer); }
   hipFree(s->d_ly_r[0]); hipFree(s->d_ly_r[1]); hipFree(s->d_ly_r[2]); hipFree(s->d_prev); hipFree(s->d_ovf_list); hipFree(s->d_ovf_list2);

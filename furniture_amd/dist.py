@@ -87,8 +87,8 @@ def step_wait_and_gather(sim, obs, reward, done, tag=0, stream=None, group=None)
         raise NotImplementedError("step_wait_and_gather: normal / shaded images are not part of the multi-GPU gather; render them on each rank instead")
     if getattr(sim, "flow", None) is not None:
         raise NotImplementedError("step_wait_and_gather: flow / velocity images are not part of the multi-GPU gather; render them on each rank instead")
-    from .envs import SENSOR_FAMILIES
-    for f in SENSOR_FAMILIES:
+    from .envs import ALL_SENSOR_FAMILIES
+    for f in ALL_SENSOR_FAMILIES:
         if getattr(sim, f.attr, None) is not None:
             raise NotImplementedError("step_wait_and_gather: %s are not part of the multi-GPU gather; %s them on each rank instead" % (f.gathered, f.verb))
     sim.sync()

@@ -39,6 +39,12 @@ SENSOR_FAMILIES = (
     SensorFamily("contacts", "contacts", "ContactSet", "contacts", "set_contacts", "contact_shapes", "contact_forces", "_con_out", "contact", "contact set", "contact-force outputs", "compute"),
     SensorFamily("wrenches", "wrench", "WrenchSet", "wrench_set", "set_wrenches", "wrench_shapes", "wrenches", "_wr_out", "wrench", "wrench set", "wrench-sensor outputs", "compute"),
 )
+# The families added after those seven, in the same terms; the loops of the env layer, of the VecEnv wrapper, of the mixed batch and of the
+# multi-GPU gather run over ALL_SENSOR_FAMILIES.
+MORE_SENSOR_FAMILIES = (
+    SensorFamily("momenta", "momentum", "MomentumSet", "momenta_set", "set_momenta", "momentum_shapes", "momenta", "_mom_out", "momentum", "momentum set", "momentum-sensor outputs", "compute"),
+)
+ALL_SENSOR_FAMILIES = SENSOR_FAMILIES + MORE_SENSOR_FAMILIES
 
 # furniture/config/furniture.py defaults that matter on the hot path (file:line in the reference)
 DEFAULTS = dict(
@@ -382,9 +388,10 @@ class FurnitureBatchEnv:
     dynamics = None
     contacts = None
     wrenches = None
+    momenta = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, contacts=None, wrenches=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, contacts=None, wrenches=None, momenta=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -443,7 +450,11 @@ class FurnitureBatchEnv:
         accelerometer: +9.81 along world z at rest), wrench_angacc (float32 [n, S, 3]), wrench_status (int32 [n], the bits of
         contact_status) and, with external=True / joint=True in the set, wrench_external (float32 [n, S, 6], the net world-frame force and
         torque of contacts, welds and applied forces on the sensor's body) and wrench_qacc / wrench_qfrc_constraint (float32 [n, nv]),
-        from one fsim_wrenches call."""
+        from one fsim_wrenches call.
+        momenta: a furniture_amd.momentum.MomentumSet (needs none of the others) -- the observations then also hold mom_com, mom_linvel
+        and mom_angmom (float32 [n, S, 3]: the centre of mass of each sensor's set of bodies, its velocity and the set's angular momentum
+        about it, world frame, at the state the observation describes) and, with jacobian=True / energy=True in the set, mom_jac (float32
+        [n, S, 3, nv], mom_linvel = mom_jac @ qvel) and mom_energy (float32 [n, 2], potential then kinetic), from one fsim_momenta call."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -456,8 +467,8 @@ class FurnitureBatchEnv:
         if flow is not None:
             from .flow import check as check_flow
             check_flow(flow, list(cameras) if cameras else None)
-        sensors = dict(rays=rays, probes=probes, pairs=pairs, frames=frames, dynamics=dynamics, contacts=contacts, wrenches=wrenches)
-        for f in SENSOR_FAMILIES:
+        sensors = dict(rays=rays, probes=probes, pairs=pairs, frames=frames, dynamics=dynamics, contacts=contacts, wrenches=wrenches, momenta=momenta)
+        for f in ALL_SENSOR_FAMILIES:
             if sensors[f.kw] is not None:
                 importlib.import_module("." + f.module, __package__).check(sensors[f.kw])
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
@@ -576,7 +587,7 @@ class FurnitureBatchEnv:
                 for k, (sh, dt) in shapes().items():
                     out[k] = torch.empty((num_envs,) + sh, dtype=dt, device=dev)
                 setattr(self, bufs, out)
-        for f in SENSOR_FAMILIES:  # (without a family: no allocation, no launch, the same observation dict)
+        for f in ALL_SENSOR_FAMILIES:  # (without a family: no allocation, no launch, the same observation dict)
             setattr(self, f.kw, sensors[f.kw])
             if sensors[f.kw] is not None:
                 getattr(self.sim, f.set)(sensors[f.kw])
@@ -634,7 +645,7 @@ class FurnitureBatchEnv:
                   "pair_distance": (-np.inf, dmax(self.pairs)), "pair_geoms": geom, "pair_normal": unit,
                   "contact_touch": force, "con_fn": force, "contact_count": (0, self.sim.max_contacts), "contact_status": status, "con_geoms": geom,
                   "wrench_status": status}  # (frame_quat: a unit quaternion up to float32 rounding, so unbounded like the rest)
-        for f in SENSOR_FAMILIES:
+        for f in ALL_SENSOR_FAMILIES:
             if getattr(self, f.kw) is not None:
                 for k, (sh, dt) in getattr(self.sim, f.shapes)().items():
                     lo, hi = bounds.get(k, (-np.inf, np.inf))
@@ -657,7 +668,8 @@ class FurnitureBatchEnv:
         is given (from one fsim_probe_distance call) and the pair sensors' outputs when a pair set is given (from one fsim_pair_distance
         call) and the frame sensors' outputs when a frame set is given (from one fsim_frame_state call) and the dynamics tensors when a
         Dynamics is given (from one fsim_dynamics call) and the contact sensors' outputs when a contact set is given (from one
-        fsim_contact_forces call) and the wrench sensors' outputs when a wrench set is given (from one fsim_wrenches call)"""
+        fsim_contact_forces call) and the wrench sensors' outputs when a wrench set is given (from one fsim_wrenches call) and the momentum
+        sensors' outputs when a momentum set is given (from one fsim_momenta call)"""
         out = self._split(self._obs, subtask)
         if self.point_cloud is not None:
             res = self.sim.render_points(images=True, out=self._pts_out)
@@ -683,7 +695,7 @@ class FurnitureBatchEnv:
                 out["point_cloud_velocity"] = self._at_points(res["camera_velocity"])
         if self.cameras and self.point_cloud is None and self.voxels is None and self.normals is None and self.flow is None:
             out["camera_depth"], out["camera_segmentation"] = self.sim.render(out=self._cam_out)
-        for f in SENSOR_FAMILIES:  # one library call each; independent of the cameras and of each other, they read the records only
+        for f in ALL_SENSOR_FAMILIES:  # one library call each; independent of the cameras and of each other, they read the records only
             if getattr(self, f.kw) is not None:
                 out.update(getattr(self.sim, f.call)(out=getattr(self, f.buf)))
         return out
@@ -1031,7 +1043,7 @@ class _SingleEnv:
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
                                          point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow,
-                                         **{f.kw: getattr(old, f.kw) for f in SENSOR_FAMILIES})
+                                         **{f.kw: getattr(old, f.kw) for f in ALL_SENSOR_FAMILIES})
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

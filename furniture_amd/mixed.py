@@ -18,7 +18,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .envs import SENSOR_FAMILIES, FurnitureBatchEnv, make_config
+from .envs import ALL_SENSOR_FAMILIES, FurnitureBatchEnv, make_config
 
 
 def lane_assignment(num_envs, k, first_env_index=0):
@@ -53,7 +53,7 @@ class FurnitureMixedBatchEnv:
         if kw.pop("flow", None) is not None:
             raise NotImplementedError("flow= is not supported by the mixed-furniture batch (one camera set per FurnitureBatchEnv): "
                                       "make one FurnitureBatchEnv per furniture instead")
-        for f in SENSOR_FAMILIES:
+        for f in ALL_SENSOR_FAMILIES:
             if kw.pop(f.kw, None) is not None:
                 raise NotImplementedError("%s= is not supported by the mixed-furniture batch (one %s per FurnitureBatchEnv): "
                                           "make one FurnitureBatchEnv per furniture instead" % (f.kw, f.one))

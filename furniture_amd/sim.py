@@ -108,6 +108,14 @@ class FsimWrenchOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in WRENCH_OUT_FIELDS]
 
 
+MOMENTUM_OUT_FIELDS = ("com", "linvel", "angmom", "jac", "energy")
+
+
+class FsimMomentumOut(ctypes.Structure):
+    """fsim_momentum_out_t (include/fsim_momentum.h): device pointers, None = not asked for"""
+    _fields_ = [(k, ctypes.c_void_p) for k in MOMENTUM_OUT_FIELDS]
+
+
 def library_path():
     return _LIBPATH
 
@@ -115,7 +123,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h", "fsim_contacts.h", "fsim_wrench.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h", "fsim_contacts.h", "fsim_wrench.h", "fsim_momentum.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -235,6 +243,8 @@ def lib():
         L.fsim_contact_forces.argtypes = [ctypes.c_void_p, ctypes.POINTER(FsimContactOut)]
         L.fsim_set_wrenches.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.fsim_wrenches.argtypes = [ctypes.c_void_p, ctypes.POINTER(FsimWrenchOut)]
+        L.fsim_set_momenta.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.fsim_momenta.argtypes = [ctypes.c_void_p, ctypes.POINTER(FsimMomentumOut)]
         _LIB = L
     return _LIB
 
@@ -272,6 +282,8 @@ DYN_SYMBOLS = ["fsim_set_dynamics", "fsim_dynamics"]
 CONTACT_SYMBOLS = ["fsim_set_contacts", "fsim_contact_forces"]
 # the wrench-sensor entry points: a header of their own (include/fsim_wrench.h), exported by the same library
 WRENCH_SYMBOLS = ["fsim_set_wrenches", "fsim_wrenches"]
+# the momentum-sensor entry points: a header of their own (include/fsim_momentum.h), exported by the same library
+MOMENTUM_SYMBOLS = ["fsim_set_momenta", "fsim_momenta"]
 
 
 def preassembled_rows(model, preassembled):
@@ -722,9 +734,9 @@ class FSim:
             raise FsimError("render_flow: no cameras set (FSim.set_cameras)")
         return self._render_derived("render_flow", lib().fsim_render_flow, ("camera_flow", "camera_velocity"), self.flow_shapes(), images, out)
 
-    # -- what the state-sensor families below share (rays, probes, pairs, frames, dynamics, contacts, wrenches) ---------------------------
+    # -- what the state-sensor families below share (rays, probes, pairs, frames, dynamics, contacts, wrenches, momenta) ------------------
     def _set_sensors(self, fn, attr, spec, cls, install):
-        """The part the seven set_X share.  None clears the library's set (n = 0: it ignores the other arguments) and the attribute;
+        """The part the set_X of these families share.  None clears the library's set (n = 0: it ignores the other arguments) and the attribute;
         anything but a `cls` is refused; install() builds the tables and hands them to fn, and only then is the spec stored."""
         if spec is None:
             self._chk(fn(self._h, *[0 if t is ctypes.c_int else None for t in fn.argtypes[1:]]))
@@ -1034,6 +1046,39 @@ class FSim:
             raise FsimError("wrenches: no sensor set (FSim.set_wrenches)")
         res = self._sensor_outputs("wrenches", self.wrench_shapes(), out)
         self._sensor_call(lib().fsim_wrenches, ctypes.byref(FsimWrenchOut(*self._ptrs(res, ["wrench_" + f for f in WRENCH_OUT_FIELDS]))))
+        return res
+
+    # -- centre-of-mass, momentum and energy sensors (include/fsim_momentum.h, furniture_amd/momentum.py) --------------------------------
+    momenta_set = None
+
+    def set_momenta(self, momentum_set):
+        """Replace the handle's momentum sensors (a furniture_amd.momentum.MomentumSet; None clears them); checked on the host first, then
+        by the library.  Independent of the cameras and of every other sensor family."""
+        from .momentum import MomentumSet, sensor_table
+
+        def install():
+            adr, bodies, subtree = sensor_table(self.cm, momentum_set)
+            self._chk(lib().fsim_set_momenta(self._h, len(adr) - 1, adr.ctypes.data, bodies.ctypes.data, subtree.ctypes.data))
+        self._set_sensors(lib().fsim_set_momenta, "momenta_set", momentum_set, MomentumSet, install)
+
+    def momentum_shapes(self):
+        """{key: (shape, dtype)} of momenta's outputs (without the n_envs dimension)"""
+        torch = self.torch
+        if self.momenta_set is None:
+            raise FsimError("momentum_shapes: no sensor set (FSim.set_momenta)")
+        s, f = self.momenta_set.n_sensors, torch.float32
+        shapes = dict(mom_com=((s, 3), f), mom_linvel=((s, 3), f), mom_angmom=((s, 3), f), mom_jac=((s, 3, self.nv), f), mom_energy=((2,), f))
+        return {key: shapes[key] for key in self.momenta_set.keys()}
+
+    def momenta(self, out=None):
+        """The momentum sensors of every env (include/fsim_momentum.h), for the state sync() leaves -> dict of device tensors: mom_com,
+        mom_linvel, mom_angmom (float32 [n, S, 3], world frame) and, with the set's jacobian=True, mom_jac (float32 [n, S, 3, nv]), with
+        energy=True mom_energy (float32 [n, 2], potential then kinetic).  out: a dict of tensors to write into, whose keys alone are
+        computed.  One launch on the handle's stream; reads the env records, writes nothing but the outputs."""
+        if self.momenta_set is None:
+            raise FsimError("momenta: no sensor set (FSim.set_momenta)")
+        res = self._sensor_outputs("momenta", self.momentum_shapes(), out)
+        self._sensor_call(lib().fsim_momenta, ctypes.byref(FsimMomentumOut(*self._ptrs(res, ["mom_" + f for f in MOMENTUM_OUT_FIELDS]))))
         return res
 
     def kernel_time_ms(self):

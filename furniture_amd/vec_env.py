@@ -8,7 +8,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .envs import GYM_IDS, REGISTRY, SENSOR_FAMILIES, FurnitureBatchEnv, make_config
+from .envs import ALL_SENSOR_FAMILIES, GYM_IDS, REGISTRY, FurnitureBatchEnv, make_config
 from .sim import INFO_EPISODE_REWARD_F
 
 
@@ -57,7 +57,7 @@ class FurnitureVecEnv:
         if kw.pop("flow", None) is not None:
             raise NotImplementedError("flow= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                       "FurnitureBatchEnv(..., cameras=[...], flow=Flow(...)), whose images stay on the device")
-        for f in SENSOR_FAMILIES:
+        for f in ALL_SENSOR_FAMILIES:
             if kw.pop(f.kw, None) is not None:
                 raise NotImplementedError("%s= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                           "FurnitureBatchEnv(..., %s=%s(...)), whose %s outputs stay on the device" % (f.kw, f.kw, f.cls, f.noun))
