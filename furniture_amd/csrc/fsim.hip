@@ -1709,6 +1709,7 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
   return FSIM_OK;
 }
 
+#include "fsim_kin.hpp"
 #include "fsim_camera.hpp"
 #include "fsim_points.hpp"
 #include "fsim_voxels.hpp"

@@ -4,7 +4,8 @@
 // Two launches per fsim_render, both on the handle's stream:
 //   k_cam_pose  one wave per env: qpos of the env record (read only) -> world pose of every colliding geom and of every camera, with
 //               the arithmetic of fs_kinematics + fs_collide (pointer doubling up the reduced tree, qnormalized on free joints and on
-//               every composition, geom pose = body pose (x) geom offset), into the handle's scratch buffer;
+//               every composition, geom pose = body pose (x) geom offset), into the handle's scratch buffer.  Its body-pose stages (A)
+//               and (B) are the functions of fsim_kin.hpp, which k_cam_twist, k_frame_state, k_dynamics and k_momenta call too;
 //   k_cam_ray   one 256-thread workgroup per (env, camera, 32 x 32 pixel tile): the env's geom table is staged in LDS, each wave culls
 //               it against the frustum of its 16 x 16 quarter into a wave-uniform list (bounding spheres; planes always kept) and each
 //               lane casts the rays of four pixels of one column against that list in closed form, in the geom's frame.
@@ -21,9 +22,10 @@ enum { CGW_POS = 0, CGW_MAT = 3, CGW_SIZE = 12, CGW_RB = 15, CGW_TYPE = 16, CGW_
 enum { CCW_RBODY = 0, CCW_CURSOR = 1, CCW_POS = 2, CCW_QUAT = 5, CCW_WORDS = 12 }; // d_cams rows (ints as float bits)
 
 struct CamPoseArgs {
-  const int *r_parent, *r_jtype, *r_qposadr, *cg_body, *cg_cursor;
-  const float *r_pos, *r_quat, *r_jaxis, *r_jpos, *cg_pos, *cg_mat, *cursor_pos0;
-  int nr, maxdepth, ncg, ncam, stride, qpos, ecpos /* Cursor agent: EC_POS of the record, else -1 */, pstride;
+  KinArgs kin;
+  const int *cg_body, *cg_cursor;
+  const float *cg_pos, *cg_mat, *cursor_pos0;
+  int ncg, ncam, ecpos /* Cursor agent: EC_POS of the record, else -1 */, pstride;
 };
 
 __global__ __launch_bounds__(64) void k_cam_pose(CamPoseArgs a, const float *__restrict__ state, const float *__restrict__ cams,
@@ -31,44 +33,14 @@ __global__ __launch_bounds__(64) void k_cam_pose(CamPoseArgs a, const float *__r
   __shared__ float sp[3 * 32], sq[4 * 32];
   __shared__ int sanc[32];
   const int e = blockIdx.x, b = threadIdx.x;
-  const float *rec = state + (size_t)e * a.stride;
+  const float *rec = state + (size_t)e * a.kin.stride;
   float *out = pose + (size_t)e * a.pstride;
-  // (A) joint transform relative to the parent (fs_kinematics; the record is never written: the free-joint quaternion is
-  //     normalised in registers, as fs_kinematics does in LDS)
-  const bool on = b < a.nr && b > 0;
-  const int bb = on ? b : 0;
-  V3 P = v3(0, 0, 0);
-  Q4 Q = q4(1, 0, 0, 0);
-  if (on) {
-    const int jt = a.r_jtype[bb], qa = a.r_qposadr[bb];
-    if (jt == JT_FREE) {
-      P = ldv3(rec + a.qpos + qa);
-      Q = qnormalized(ldq(rec + a.qpos + qa + 3));
-    } else {
-      const Q4 q0 = ldq(a.r_quat + 4 * bb);
-      const V3 p0 = ldv3(a.r_pos + 3 * bb), jpos = ldv3(a.r_jpos + 3 * bb), jax = ldv3(a.r_jaxis + 3 * bb);
-      const V3 al = p0 + qrot(q0, jpos), axl = qrot(q0, jax);
-      const float q = rec[a.qpos + qa];
-      if (jt == JT_SLIDE) { Q = q0; P = p0 + axl * q; }
-      else { Q = qmul(q0, axisangle(jax, q)); P = al - qrot(Q, jpos); }
-    }
-  }
-  // (B) world poses by pointer doubling up the tree
-  int anc = on ? a.r_parent[bb] : 0;
-  for (int span = 1; span < a.maxdepth; span <<= 1) {
-    if (b < a.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); sanc[b] = anc; }
-    __syncthreads();
-    if (anc > 0) {
-      const V3 pa = ldv3(sp + 3 * anc);
-      const Q4 qa_ = ldq(sq + 4 * anc);
-      const int na = sanc[anc];
-      P = pa + qrot(qa_, P);
-      Q = qnormalized(qmul(qa_, Q));
-      anc = na;
-    }
-    __syncthreads();
-  }
-  if (b < a.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); }
+  // (A) joint transform relative to the parent, (B) world poses by pointer doubling up the tree: fsim_kin.hpp
+  V3 P;
+  Q4 Q;
+  const KinLane l = kin_joint_pose(a.kin, rec, b, &P, &Q);
+  kin_world_poses(a.kin, l, b, sp, sq, sanc, &P, &Q);
+  if (b < a.kin.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); }
   __syncthreads();
   // (C) colliding geoms (fs_collide): body pose (x) geom offset; cursor boxes follow the env's cursor position
   for (int g = b; g < a.ncg; g += 64) {
@@ -313,8 +285,8 @@ static int cam_mount_tables(const fsim *s, CamMountTables &t) {
 // k_cam_pose's arguments for the handle's model: nframes mounted frames (cameras, sensors) behind the geoms, pstride words per env
 static CamPoseArgs cam_pose_args(const fsim *s, int nframes, int pstride) {
   const DModel &m = s->m;
-  return CamPoseArgs{m.r_parent, m.r_jtype, m.r_qposadr, m.cg_body, m.cg_cursor, m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.cg_pos, m.cg_mat, m.cursor_pos0,
-                     m.nr, m.maxdepth, m.ncg, nframes, s->ly.stride, s->ly.qpos, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1, pstride};
+  return CamPoseArgs{kin_args(s), m.cg_body, m.cg_cursor, m.cg_pos, m.cg_mat, m.cursor_pos0,
+                     m.ncg, nframes, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1, pstride};
 }
 
 // One d_cams row (CCW_*) of a frame (pos, quat wxyz) given in the frame of model body `body` (-1: the world), composed in double.

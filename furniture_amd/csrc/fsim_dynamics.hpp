@@ -3,10 +3,10 @@
 //
 // One launch per fsim_dynamics, on the handle's stream:
 //   k_dynamics  one wave per env, like k_frame_state.  qpos / qvel of the env record (read only).  The stages are those of k_frame_state and
-//               of the step's fs_com_inertia / fs_crb_factor / fs_velocity_bias, written out here on their own (DESIGN.md 11, 15 and 19
-//               record what sharing a loop did to existing kernels):
-//               (A) + (B) world pose of every reduced body by pointer doubling; (C) inertial-frame origins; (D) per-tree centre of mass,
-//               the reference point of every spatial vector of the tree (what keeps fp32 honest far from the origin); (E) body inertias
+//               of the step's fs_com_inertia / fs_crb_factor / fs_velocity_bias; the latter, which run on the step's own context, are
+//               written out here (DESIGN.md 11, 15 and 19 record what sharing a loop did to existing kernels):
+//               (A) + (B) world pose of every reduced body by pointer doubling (fsim_kin.hpp); (C) inertial-frame origins; (D) per-tree
+//               centre of mass, the reference point of every spatial vector of the tree (what keeps fp32 honest far from the origin); (E) body inertias
 //               about it and the motion axes of every dof, a model with nv > 64 taking a second round; (F) composite inertias of every
 //               body's strict descendants through the subtree masks (unsigned: body 31 is the top bit); (G) lane = dof i: row i of the
 //               packed per-tree lower triangle of M, M_ij = cdof_j . (crb_body(i) cdof_i) + the share of body(i) itself, where body(j) is
@@ -26,10 +26,11 @@
 #include "../../include/fsim_dynamics.h"
 
 struct DynArgs {
-  const int *r_parent, *r_jtype, *r_qposadr, *r_dofadr, *r_ancmask, *r_tree, *dof_rbody, *tree_bodyadr, *tree_bodynum;
-  const float *r_pos, *r_quat, *r_jaxis, *r_jpos, *r_mass, *r_ipos, *r_inertia, *dof_armature;
+  KinArgs kin;
+  const int *r_ancmask, *r_tree, *dof_rbody, *tree_bodyadr, *tree_bodynum;
+  const float *r_mass, *r_ipos, *r_inertia, *dof_armature;
   const int *tab; // [2 * nv]: per dof (first dof of its tree | dofs of the tree << 8), first word of the tree's packed triangle; then [K]: the selection
-  int nr, maxdepth, nv, ntree, K, W /* words of all packed triangles */, maxn /* dofs of the largest tree */, stride, qpos, qvel;
+  int nv, ntree, K, W /* words of all packed triangles */, maxn /* dofs of the largest tree */;
   float g[3];
 };
 
@@ -43,53 +44,24 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
   __shared__ int sanc[32], sdb[FSIM_DYN_MAX_NV], st0[FSIM_DYN_MAX_NV], st1[FSIM_DYN_MAX_NV], ssel[FSIM_DYN_MAX_NV];
   __shared__ unsigned ssub[32], sam[32];
   const int e = blockIdx.x, b = threadIdx.x;
-  const float *rec = state + (size_t)e * a.stride;
+  const float *rec = state + (size_t)e * a.kin.stride;
   float *Mt = dyn_tri, *Lt = dyn_tri + a.W, *Xt = dyn_tri + 2 * a.W;
   const bool want_m = mass || minv, want_b = bias != nullptr, want_f = bias || gravity;
   for (int d = b; d < a.nv; d += 64) { sdb[d] = a.dof_rbody[d]; st0[d] = a.tab[2 * d]; st1[d] = a.tab[2 * d + 1]; }
   for (int k = b; k < a.K; k += 64) ssel[k] = a.tab[2 * a.nv + k];
-  // (A) + (B) of k_frame_state
-  const bool on = b < a.nr && b > 0;
-  const int bb = on ? b : 0;
-  const int jt = a.r_jtype[bb], qa = a.r_qposadr[bb], da = a.r_dofadr[bb], parent = a.r_parent[bb];
-  const V3 jpos = ldv3(a.r_jpos + 3 * bb), jax = ldv3(a.r_jaxis + 3 * bb);
-  V3 P = v3(0, 0, 0);
-  Q4 Q = q4(1, 0, 0, 0);
-  if (on) {
-    if (jt == JT_FREE) {
-      P = ldv3(rec + a.qpos + qa);
-      Q = qnormalized(ldq(rec + a.qpos + qa + 3));
-    } else {
-      const Q4 q0 = ldq(a.r_quat + 4 * bb);
-      const V3 p0 = ldv3(a.r_pos + 3 * bb);
-      const V3 al = p0 + qrot(q0, jpos), axl = qrot(q0, jax);
-      const float q = rec[a.qpos + qa];
-      if (jt == JT_SLIDE) { Q = q0; P = p0 + axl * q; }
-      else { Q = qmul(q0, axisangle(jax, q)); P = al - qrot(Q, jpos); }
-    }
-  }
-  int anc = on ? parent : 0;
-  for (int span = 1; span < a.maxdepth; span <<= 1) {
-    if (b < a.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); sanc[b] = anc; }
-    __syncthreads();
-    if (anc > 0) {
-      const V3 pa = ldv3(sp + 3 * anc);
-      const Q4 qa_ = ldq(sq + 4 * anc);
-      const int na = sanc[anc];
-      P = pa + qrot(qa_, P);
-      Q = qnormalized(qmul(qa_, Q));
-      anc = na;
-    }
-    __syncthreads();
-  }
+  // (A) + (B) the world pose of every reduced body, left in sp / sq: fsim_kin.hpp
+  V3 P;
+  Q4 Q;
+  const KinLane l = kin_joint_pose(a.kin, rec, b, &P, &Q);
+  kin_world_poses(a.kin, l, b, sp, sq, sanc, &P, &Q);
   // (C) inertial-frame origins; the subtree masks from the ancestor masks (which carry the self bit; a descendant's index is above its ancestor's)
   const M3 R = q2m(Q);
-  if (b < a.nr) {
+  if (b < a.kin.nr) {
     stv3(sp + 3 * b, P);
     stq(sq + 4 * b, Q);
-    stv3(sxi + 3 * b, P + mulv(R, ldv3(a.r_ipos + 3 * bb)));
+    stv3(sxi + 3 * b, P + mulv(R, ldv3(a.r_ipos + 3 * l.bb)));
     unsigned sub = 0;
-    for (int d = b; d < a.nr; d++)
+    for (int d = b; d < a.kin.nr; d++)
       if (b > 0 && (((unsigned)a.r_ancmask[d] >> b) & 1u)) sub |= 1u << d;
     ssub[b] = sub;
     sam[b] = (unsigned)a.r_ancmask[b];
@@ -109,7 +81,7 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
   }
   __syncthreads();
   // (E) body inertias about the tree's centre of mass: Ixx Iyy Izz Ixy Ixz Iyz hx hy hz m (inert_mul's record); motion axes of every dof
-  if (b < a.nr) {
+  if (b < a.kin.nr) {
     float *I = sI + 10 * b;
     if (b == 0) {
       for (int k = 0; k < 10; k++) I[k] = 0.0f;
@@ -133,7 +105,7 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
     }
   }
   for (int d = b; d < a.nv; d += 64) {
-    const int db = sdb[d], djt = a.r_jtype[db], k = d - a.r_dofadr[db];
+    const int db = sdb[d], djt = a.kin.r_jtype[db], k = d - a.kin.r_dofadr[db];
     const V3 Pb = ldv3(sp + 3 * db), com = ldv3(scom + 3 * a.r_tree[db]);
     const Q4 Qb = ldq(sq + 4 * db);
     S6 s;
@@ -144,9 +116,9 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
       if (k < 3) s.l = ax;
       else { axb = ax; s.a = qrot(Qb, ax); s.l = cross(s.a, com - Pb); }
     } else {
-      const V3 axl = ldv3(a.r_jaxis + 3 * db), ax = qrot(Qb, axl);
+      const V3 axl = ldv3(a.kin.r_jaxis + 3 * db), ax = qrot(Qb, axl);
       if (djt == JT_SLIDE) s.l = ax;
-      else { axb = axl; s.a = ax; s.l = cross(ax, com - (Pb + qrot(Qb, ldv3(a.r_jpos + 3 * db)))); }
+      else { axb = axl; s.a = ax; s.l = cross(ax, com - (Pb + qrot(Qb, ldv3(a.kin.r_jpos + 3 * db)))); }
     }
     sts6(scdof + 6 * d, s);
     stv3(sax + 3 * d, axb);
@@ -154,7 +126,7 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
   __syncthreads();
   if (want_m) {
     // (F) composite inertias of the strict descendants
-    if (b < a.nr) {
+    if (b < a.kin.nr) {
       float acc[10];
       for (int k = 0; k < 10; k++) acc[k] = 0.0f;
       for (unsigned mm = ssub[b] & ~(1u << b); mm; mm &= mm - 1) {
@@ -195,9 +167,10 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
     // (H) body velocities U and velocity-product accelerations C by the chain rule (U, C) o (U', C') = (U + U', C + C' + U x U')
     S6 u = s6zero(), cc = s6zero();
     if (want_b) {
-      if (on) {
-        const float *qv = rec + a.qvel + da;
-        if (jt == JT_FREE) {
+      if (l.on) {
+        const int da = l.da;
+        const float *qv = rec + a.kin.qvel + da;
+        if (l.jt == JT_FREE) {
           S6 vt = s6zero();
 #pragma unroll
           for (int t = 0; t < 3; t++) vt = vt + lds6(scdof + 6 * (da + t)) * qv[t];
@@ -211,9 +184,9 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
         } else
           u = lds6(scdof + 6 * da) * qv[0];
       }
-      anc = on ? parent : 0;
-      for (int span = 1; span < a.maxdepth; span <<= 1) {
-        if (b < a.nr) { sts6(sU + 6 * b, u); sts6(sCC + 6 * b, cc); sanc[b] = anc; }
+      int anc = l.anc;
+      for (int span = 1; span < a.kin.maxdepth; span <<= 1) {
+        if (b < a.kin.nr) { sts6(sU + 6 * b, u); sts6(sCC + 6 * b, cc); sanc[b] = anc; }
         __syncthreads();
         if (anc > 0) {
           const S6 ua = lds6(sU + 6 * anc), ca = lds6(sCC + 6 * anc);
@@ -225,7 +198,7 @@ __global__ __launch_bounds__(64) void k_dynamics(DynArgs a, const float *__restr
         __syncthreads();
       }
     }
-    if (b < a.nr) {
+    if (b < a.kin.nr) {
       S6 ag = s6zero();
       ag.l = v3(-a.g[0], -a.g[1], -a.g[2]);
       const float *I = sI + 10 * b;
@@ -356,9 +329,8 @@ extern "C" int fsim_dynamics(fsim_t *s, float *mass_dev, float *minv_dev, float 
   { int rc_ = settle(s); if (rc_) return rc_; } // the state fsim_sync leaves: overflowed envs re-stepped first
   const DynState &k = *s->dyn;
   const DModel &m = s->m;
-  DynArgs da{m.r_parent, m.r_jtype, m.r_qposadr, m.r_dofadr, m.r_ancmask, m.r_tree, m.dof_rbody, m.tree_bodyadr, m.tree_bodynum,
-             m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.r_mass, m.r_ipos, m.r_inertia, m.dof_armature, k.d_tab,
-             m.nr, m.maxdepth, m.nv, m.ntree, k.K, k.W, k.maxn, s->ly.stride, s->ly.qpos, s->ly.qvel, {m.gravity[0], m.gravity[1], m.gravity[2]}};
+  DynArgs da{kin_args(s), m.r_ancmask, m.r_tree, m.dof_rbody, m.tree_bodyadr, m.tree_bodynum, m.r_mass, m.r_ipos, m.r_inertia, m.dof_armature, k.d_tab,
+             m.nv, m.ntree, k.K, k.W, k.maxn, {m.gravity[0], m.gravity[1], m.gravity[2]}};
   const size_t lds = 4 * (size_t)3 * k.W; // M, L and X: 1.8 KB for Sawyer + table_lack_0825, 4.1 KB for Baxter + table_liden_0921, at most 20 KB for 128 dofs in trees of 25
   hipLaunchKernelGGL(k_dynamics, dim3(s->n_envs), dim3(64), lds, s->stream, da, s->d_state, mass_dev, minv_dev, bias_dev, gravity_dev);
   HIPCHK(hipGetLastError());

@@ -5,8 +5,9 @@
 //
 // After fsim_render's two launches, on the same stream:
 //   k_cam_twist  one wave per env, like k_cam_pose: qpos of the env record (read only) -> world pose of every reduced body (stages (A)
-//                and (B) of k_cam_pose, written out a second time), qvel -> each body's own joint twist expressed about the WORLD ORIGIN,
-//                so that the twists of a chain add; one more pointer-doubling round set over r_parent sums them with plain sums.  Out:
+//                and (B) of k_cam_pose: fsim_kin.hpp), qvel -> each body's own joint twist expressed about the WORLD ORIGIN, so that
+//                the twists of a chain add; one more pointer-doubling round set over r_parent sums them with plain sums (stages (T)
+//                and (U), in fsim_kin.hpp too: k_frame_state runs them as well).  Out:
 //                6 words (v at the origin of the pose row, w) per colliding geom and per camera, [n_envs][ncg + ncam][6].
 //   k_cam_flow   one 256-thread workgroup per (env, camera, chunk of up to FLW_CHUNK pixels), the shape of k_cam_normal.  The geom
 //                origins, the geom and camera twists, the camera poses and the model-geom-id -> colliding-geom table are staged in LDS
@@ -22,8 +23,7 @@
 
 struct FlwTwistArgs {
   CamPoseArgs p;
-  const int *r_dofadr;
-  int qvel /* offset of qvel in the record */, tstride /* twist words per env */;
+  int tstride /* twist words per env */;
 };
 
 __global__ __launch_bounds__(64) void k_cam_twist(FlwTwistArgs t, const float *__restrict__ state, const float *__restrict__ cams,
@@ -32,76 +32,17 @@ __global__ __launch_bounds__(64) void k_cam_twist(FlwTwistArgs t, const float *_
   __shared__ int sanc[32];
   const CamPoseArgs &a = t.p;
   const int e = blockIdx.x, b = threadIdx.x;
-  const float *rec = state + (size_t)e * a.stride;
+  const float *rec = state + (size_t)e * a.kin.stride;
   const float *P0 = pose + (size_t)e * a.pstride; // what k_cam_pose wrote for this env in this very call
   float *out = twist + (size_t)e * t.tstride;
-  // (A) + (B) of k_cam_pose, a second time (a device function shared with k_cam_pose would have to leave that kernel's code as it is:
-  //     DESIGN.md 11 records how a shared loop changed k_cam_ray).  k_cam_pose keeps the geoms' and cameras' poses only; the joint twists
-  //     need every reduced body's.
-  const bool on = b < a.nr && b > 0;
-  const int bb = on ? b : 0;
-  const int jt = a.r_jtype[bb], qa = a.r_qposadr[bb], da = t.r_dofadr[bb], parent = a.r_parent[bb];
-  const V3 jpos = ldv3(a.r_jpos + 3 * bb), jax = ldv3(a.r_jaxis + 3 * bb);
-  V3 P = v3(0, 0, 0);
-  Q4 Q = q4(1, 0, 0, 0);
-  if (on) {
-    if (jt == JT_FREE) {
-      P = ldv3(rec + a.qpos + qa);
-      Q = qnormalized(ldq(rec + a.qpos + qa + 3));
-    } else {
-      const Q4 q0 = ldq(a.r_quat + 4 * bb);
-      const V3 p0 = ldv3(a.r_pos + 3 * bb);
-      const V3 al = p0 + qrot(q0, jpos), axl = qrot(q0, jax);
-      const float q = rec[a.qpos + qa];
-      if (jt == JT_SLIDE) { Q = q0; P = p0 + axl * q; }
-      else { Q = qmul(q0, axisangle(jax, q)); P = al - qrot(Q, jpos); }
-    }
-  }
-  int anc = on ? parent : 0;
-  for (int span = 1; span < a.maxdepth; span <<= 1) {
-    if (b < a.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); sanc[b] = anc; }
-    __syncthreads();
-    if (anc > 0) {
-      const V3 pa = ldv3(sp + 3 * anc);
-      const Q4 qa_ = ldq(sq + 4 * anc);
-      const int na = sanc[anc];
-      P = pa + qrot(qa_, P);
-      Q = qnormalized(qmul(qa_, Q));
-      anc = na;
-    }
-    __syncthreads();
-  }
-  // (T) the body's own joint twist: w, and v0 = the velocity of the body-fixed point that is at the world origin now.  A twist about
-  //     one common point is a plain 6-vector: those of a chain add.  (P, Q) is the body's world pose; a hinge or slide axis is the
-  //     same in the body's frame before and after its own joint moved, so R_b axis needs no parent.
-  V3 w = v3(0, 0, 0), v0 = v3(0, 0, 0);
-  if (on) {
-    const float *qv = rec + t.qvel + da;
-    if (jt == JT_FREE) { // qvel[0:3]: world velocity of the body origin; qvel[3:6]: angular velocity in the body's own frame
-      w = qrot(Q, ldv3(qv + 3));
-      v0 = ldv3(qv) - cross(w, P);
-    } else if (jt == JT_SLIDE) {
-      v0 = qrot(Q, jax) * qv[0];
-    } else { // hinge, about the anchor x_b + R_b jpos
-      w = qrot(Q, jax) * qv[0];
-      v0 = cross(P + qrot(Q, jpos), w);
-    }
-  }
-  // (U) sum up the tree, by pointer doubling as (B) (and as fs_velocity_bias sums its spatial velocities)
-  anc = on ? parent : 0;
-  for (int span = 1; span < a.maxdepth; span <<= 1) {
-    if (b < a.nr) { stv3(sv + 3 * b, v0); stv3(sw + 3 * b, w); sanc[b] = anc; }
-    __syncthreads();
-    if (anc > 0) {
-      const V3 va = ldv3(sv + 3 * anc), wa = ldv3(sw + 3 * anc);
-      const int na = sanc[anc];
-      v0 = va + v0;
-      w = wa + w;
-      anc = na;
-    }
-    __syncthreads();
-  }
-  if (b < a.nr) { stv3(sv + 3 * b, v0); stv3(sw + 3 * b, w); }
+  // (A) + (B): k_cam_pose keeps the geoms' and cameras' poses only, and the joint twists need every reduced body's; then (T) the body's
+  //     own joint twist about the world origin and (U) its sum up the tree: fsim_kin.hpp
+  V3 P, v0, w;
+  Q4 Q;
+  const KinLane l = kin_joint_pose(a.kin, rec, b, &P, &Q);
+  kin_world_poses(a.kin, l, b, sp, sq, sanc, &P, &Q);
+  kin_joint_twist(a.kin, l, rec, P, Q, &v0, &w);
+  kin_sum_twists(a.kin, l, b, sv, sw, sanc, v0, w);
   __syncthreads();
   // (V) per colliding geom and per camera: the twist of its reduced body, taken at the origin of its pose row.  The cursor offset in
   //     that origin is a teleport between steps: it moves the point, it adds no velocity (the cursor bodies hang on reduced body 0).
@@ -212,7 +153,7 @@ extern "C" int fsim_render_flow(fsim_t *s, float *depth_dev, int32_t *seg_dev, f
   FlwTwistArgs ta{};
   ta.p = cam_pose_args(s, k.ncam, k.pstride);
   ta.p.ecpos = -1;
-  ta.r_dofadr = m.r_dofadr; ta.qvel = s->ly.qvel; ta.tstride = nrow * FLW_TW;
+  ta.tstride = nrow * FLW_TW;
   hipLaunchKernelGGL(k_cam_twist, dim3(s->n_envs), dim3(64), 0, s->stream, ta, s->d_state, k.d_cams, k.d_pose, v.d_twist);
   HIPCHK(hipGetLastError());
   FlwArgs fa{};

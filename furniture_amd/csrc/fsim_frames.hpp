@@ -4,10 +4,9 @@
 //
 // One launch per fsim_frame_state, on the handle's stream:
 //   k_frame_state  one wave per env, like k_cam_twist.  qpos of the env record (read only) -> world pose of every reduced body (stages (A)
-//                  and (B) of k_cam_pose, written out a third time: DESIGN.md 11 and 15 record what sharing a loop did to existing
-//                  kernels); when vel is asked for, qvel -> every body's summed twist about the WORLD ORIGIN (stages (T) and (U) of
-//                  k_cam_twist); when jac is asked for, (J) the unit twist of every dof about the world origin into LDS, 6 * nv words
-//                  (row-major [6][nv]: lanes of one round read consecutive words), a free joint contributing six columns and a model
+//                  and (B) of k_cam_pose); when vel is asked for, qvel -> every body's summed twist about the WORLD ORIGIN (stages (T)
+//                  and (U) of k_cam_twist; all four are the functions of fsim_kin.hpp); when jac is asked for, (J) the unit twist of
+//                  every dof about the world origin into LDS, 6 * nv words (row-major [6][nv]: lanes of one round read consecutive words), a free joint contributing six columns and a model
 //                  with nv > 64 taking a second round.  (S) lane s then takes sensor s: the poses of its two frames, pos and quat,
 //                  and vel from the DIFFERENCE of the two bodies' twists taken at p -- (V_f - V_g) + (W_f - W_g) x p, which is
 //                  v - v_g - w_g x r in real arithmetic and exactly 0 for two frames of one body; it leaves p, R_g and the two
@@ -25,9 +24,10 @@
 #define FRM_SW 16 // LDS words per sensor for stage (K): p 3, R_g 9, ancestor masks of F's and G's bodies, 2 unused
 
 struct FrameArgs {
-  const int *r_parent, *r_jtype, *r_qposadr, *r_dofadr, *r_ancmask, *dof_rbody;
-  const float *r_pos, *r_quat, *r_jaxis, *r_jpos, *cursor_pos0;
-  int nr, maxdepth, nv, nsens, stride, qpos, qvel, ecpos /* Cursor agent: EC_POS of the record, else -1 */;
+  KinArgs kin;
+  const int *r_ancmask, *dof_rbody;
+  const float *cursor_pos0;
+  int nv, nsens, ecpos /* Cursor agent: EC_POS of the record, else -1 */;
 };
 
 // world pose of a frame row (CCW_*): reduced body pose (x) the host-composed offset; a cursor body's frame follows the env's cursor
@@ -48,79 +48,24 @@ __global__ __launch_bounds__(64) void k_frame_state(FrameArgs a, const float *__
   __shared__ float sp[3 * 32], sq[4 * 32], sv[3 * 32], sw[3 * 32], ssen[FRM_SW * FSIM_FRAME_MAX_SENSORS];
   __shared__ int sanc[32], sdb[FSIM_FRAME_MAX_NV];
   const int e = blockIdx.x, b = threadIdx.x;
-  const float *rec = state + (size_t)e * a.stride;
-  // (A) + (B) of k_cam_pose
-  const bool on = b < a.nr && b > 0;
-  const int bb = on ? b : 0;
-  const int jt = a.r_jtype[bb], qa = a.r_qposadr[bb], da = a.r_dofadr[bb], parent = a.r_parent[bb];
-  const V3 jpos = ldv3(a.r_jpos + 3 * bb), jax = ldv3(a.r_jaxis + 3 * bb);
-  V3 P = v3(0, 0, 0);
-  Q4 Q = q4(1, 0, 0, 0);
-  if (on) {
-    if (jt == JT_FREE) {
-      P = ldv3(rec + a.qpos + qa);
-      Q = qnormalized(ldq(rec + a.qpos + qa + 3));
-    } else {
-      const Q4 q0 = ldq(a.r_quat + 4 * bb);
-      const V3 p0 = ldv3(a.r_pos + 3 * bb);
-      const V3 al = p0 + qrot(q0, jpos), axl = qrot(q0, jax);
-      const float q = rec[a.qpos + qa];
-      if (jt == JT_SLIDE) { Q = q0; P = p0 + axl * q; }
-      else { Q = qmul(q0, axisangle(jax, q)); P = al - qrot(Q, jpos); }
-    }
-  }
-  int anc = on ? parent : 0;
-  for (int span = 1; span < a.maxdepth; span <<= 1) {
-    if (b < a.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); sanc[b] = anc; }
-    __syncthreads();
-    if (anc > 0) {
-      const V3 pa = ldv3(sp + 3 * anc);
-      const Q4 qa_ = ldq(sq + 4 * anc);
-      const int na = sanc[anc];
-      P = pa + qrot(qa_, P);
-      Q = qnormalized(qmul(qa_, Q));
-      anc = na;
-    }
-    __syncthreads();
-  }
-  if (b < a.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); }
+  const float *rec = state + (size_t)e * a.kin.stride;
+  // (A) + (B) the world pose of every reduced body; when vel is asked for, (T) + (U) its summed twist about the world origin: fsim_kin.hpp
+  V3 P;
+  Q4 Q;
+  const KinLane l = kin_joint_pose(a.kin, rec, b, &P, &Q);
+  kin_world_poses(a.kin, l, b, sp, sq, sanc, &P, &Q);
+  if (b < a.kin.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); }
   if (vel) {
-    // (T) of k_cam_twist: the body's own joint twist about the world origin
-    V3 w = v3(0, 0, 0), v0 = v3(0, 0, 0);
-    if (on) {
-      const float *qv = rec + a.qvel + da;
-      if (jt == JT_FREE) { // qvel[0:3]: world velocity of the body origin; qvel[3:6]: angular velocity in the body's own frame
-        w = qrot(Q, ldv3(qv + 3));
-        v0 = ldv3(qv) - cross(w, P);
-      } else if (jt == JT_SLIDE) {
-        v0 = qrot(Q, jax) * qv[0];
-      } else { // hinge, about the anchor x_b + R_b jpos
-        w = qrot(Q, jax) * qv[0];
-        v0 = cross(P + qrot(Q, jpos), w);
-      }
-    }
-    // (U) sum up the tree by pointer doubling
-    anc = on ? parent : 0;
-    for (int span = 1; span < a.maxdepth; span <<= 1) {
-      if (b < a.nr) { stv3(sv + 3 * b, v0); stv3(sw + 3 * b, w); sanc[b] = anc; }
-      __syncthreads();
-      if (anc > 0) {
-        const V3 va = ldv3(sv + 3 * anc), wa = ldv3(sw + 3 * anc);
-        const int na = sanc[anc];
-        v0 = va + v0;
-        w = wa + w;
-        anc = na;
-      }
-      __syncthreads();
-    }
-    if (b < a.nr) { stv3(sv + 3 * b, v0); stv3(sw + 3 * b, w); }
+    V3 v0, w;
+    kin_joint_twist(a.kin, l, rec, P, Q, &v0, &w);
+    kin_sum_twists(a.kin, l, b, sv, sw, sanc, v0, w);
   }
   __syncthreads();
   // (J) the unit twist of every dof about the world origin: hinge (anchor x a, a), slide (a, 0), free translation (e_i, 0), free
   //     rotation (x_b x R_b e_i, R_b e_i)
   if (jac) {
     for (int d = b; d < a.nv; d += 64) {
-      const int db = a.dof_rbody[d], djt = a.r_jtype[db], k = d - a.r_dofadr[db];
+      const int db = a.dof_rbody[d], djt = a.kin.r_jtype[db], k = d - a.kin.r_dofadr[db];
       const V3 Pb = ldv3(sp + 3 * db);
       const Q4 Qb = ldq(sq + 4 * db);
       V3 uv = v3(0, 0, 0), uw = v3(0, 0, 0);
@@ -129,9 +74,9 @@ __global__ __launch_bounds__(64) void k_frame_state(FrameArgs a, const float *__
         if (k < 3) uv = ax;
         else { uw = qrot(Qb, ax); uv = cross(Pb, uw); }
       } else {
-        const V3 ax = qrot(Qb, ldv3(a.r_jaxis + 3 * db));
+        const V3 ax = qrot(Qb, ldv3(a.kin.r_jaxis + 3 * db));
         if (djt == JT_SLIDE) uv = ax;
-        else { uw = ax; uv = cross(Pb + qrot(Qb, ldv3(a.r_jpos + 3 * db)), ax); }
+        else { uw = ax; uv = cross(Pb + qrot(Qb, ldv3(a.kin.r_jpos + 3 * db)), ax); }
       }
       frm_ut[d] = uv.x; frm_ut[a.nv + d] = uv.y; frm_ut[2 * a.nv + d] = uv.z;
       frm_ut[3 * a.nv + d] = uw.x; frm_ut[4 * a.nv + d] = uw.y; frm_ut[5 * a.nv + d] = uw.z;
@@ -241,8 +186,7 @@ extern "C" int fsim_frame_state(fsim_t *s, float *pos_dev, float *quat_dev, floa
   { int rc_ = settle(s); if (rc_) return rc_; } // the state fsim_sync leaves: overflowed envs re-stepped first
   const FrameState &k = *s->frame;
   const DModel &m = s->m;
-  FrameArgs fa{m.r_parent, m.r_jtype, m.r_qposadr, m.r_dofadr, m.r_ancmask, m.dof_rbody, m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.cursor_pos0,
-               m.nr, m.maxdepth, m.nv, k.nsens, s->ly.stride, s->ly.qpos, s->ly.qvel, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1};
+  FrameArgs fa{kin_args(s), m.r_ancmask, m.dof_rbody, m.cursor_pos0, m.nv, k.nsens, m.agent == 2 ? s->ly.env + E_GROUP + m.nparts + EC_POS : -1};
   const size_t lds = jac_dev ? 4 * (size_t)18 * m.nv : 0; // the unit twists and the two tiles of stage (K): at most 9 KB
   hipLaunchKernelGGL(k_frame_state, dim3(s->n_envs), dim3(64), lds, s->stream, fa, s->d_state, k.d_frames, pos_dev, quat_dev, vel_dev, jac_dev);
   HIPCHK(hipGetLastError());

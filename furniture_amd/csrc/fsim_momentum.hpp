@@ -3,10 +3,10 @@
 //
 // One launch per fsim_momenta, on the handle's stream:
 //   k_momenta  one wave per env, like k_dynamics.  qpos / qvel of the env record (read only) and nothing else of it.  The stages are those of
-//              k_dynamics and of the step's fs_velocity_bias, written out here on their own (DESIGN.md 11, 15 and 19 record what sharing a
-//              loop did to existing kernels):
-//              (1) world pose of every reduced body by pointer doubling, then the inertial-frame origins x_b and the subtree masks (stages
-//              A to C of k_dynamics); (2) the motion axes of every dof about the origin of the first body of the dof's tree (the reference
+//              k_dynamics and of the step's fs_velocity_bias; the latter, which runs on the step's own context, and the chain sum, whose
+//              reference point and scratch are this kernel's own, are written out here:
+//              (1) world pose of every reduced body by pointer doubling (fsim_kin.hpp), then the inertial-frame origins x_b and the
+//              subtree masks (stages A to C of k_dynamics); (2) the motion axes of every dof about the origin of the first body of the dof's tree (the reference
 //              point of the tree's spatial vectors; a free part's own origin, so that its velocity is formed from R ipos and never from a
 //              difference of positions: the same bits 8 m out as at the origin), every body's own joint twist,
 //              the associative chain U o U' = U + U' up the ancestors by pointer doubling (stage H of k_dynamics without its acceleration
@@ -25,10 +25,11 @@
 #define MOM_MAX_NV 128 // dofs whose motion axes the pass holds (FSIM_DYN_MAX_NV; fsim_create refuses a model beyond it)
 
 struct MomArgs {
-  const int *r_parent, *r_jtype, *r_qposadr, *r_dofadr, *r_ancmask, *r_tree, *dof_rbody, *tree_bodyadr;
-  const float *r_pos, *r_quat, *r_jaxis, *r_jpos, *r_mass, *r_ipos, *r_inertia, *dof_armature;
+  KinArgs kin;
+  const int *r_ancmask, *r_tree, *dof_rbody, *tree_bodyadr;
+  const float *r_mass, *r_ipos, *r_inertia, *dof_armature;
   const unsigned *masks; // [S]: the reduced bodies of every sensor
-  int nr, maxdepth, nv, S, stride, qpos, qvel;
+  int nv, S;
   float g[3];
   fsim_momentum_out_t out;
 };
@@ -38,53 +39,26 @@ __global__ __launch_bounds__(64) void k_momenta(MomArgs a, const float *__restri
   __shared__ int sanc[32], sdb[MOM_MAX_NV], sref[32];
   __shared__ unsigned ssub[32], smask[FSIM_MOM_MAX_SENSORS];
   const int e = blockIdx.x, b = threadIdx.x;
-  const float *rec = state + (size_t)e * a.stride;
+  const float *rec = state + (size_t)e * a.kin.stride;
   for (int d = b; d < a.nv; d += 64) sdb[d] = a.dof_rbody[d];
   if (b < a.S) smask[b] = a.masks[b];
-  // (1) stages A + B of k_dynamics: the pose of every body in its parent, then in the world by pointer doubling
-  const bool on = b < a.nr && b > 0;
-  const int bb = on ? b : 0;
-  const int jt = a.r_jtype[bb], qa = a.r_qposadr[bb], da = a.r_dofadr[bb], parent = a.r_parent[bb];
-  const V3 jpos = ldv3(a.r_jpos + 3 * bb), jax = ldv3(a.r_jaxis + 3 * bb);
-  V3 P = v3(0, 0, 0);
-  Q4 Q = q4(1, 0, 0, 0);
-  if (on) {
-    if (jt == JT_FREE) {
-      P = ldv3(rec + a.qpos + qa);
-      Q = qnormalized(ldq(rec + a.qpos + qa + 3));
-    } else {
-      const Q4 q0 = ldq(a.r_quat + 4 * bb);
-      const V3 p0 = ldv3(a.r_pos + 3 * bb);
-      const V3 al = p0 + qrot(q0, jpos), axl = qrot(q0, jax);
-      const float q = rec[a.qpos + qa];
-      if (jt == JT_SLIDE) { Q = q0; P = p0 + axl * q; }
-      else { Q = qmul(q0, axisangle(jax, q)); P = al - qrot(Q, jpos); }
-    }
-  }
-  int anc = on ? parent : 0;
-  for (int span = 1; span < a.maxdepth; span <<= 1) {
-    if (b < a.nr) { stv3(sp + 3 * b, P); stq(sq + 4 * b, Q); sanc[b] = anc; }
-    __syncthreads();
-    if (anc > 0) {
-      const V3 pa = ldv3(sp + 3 * anc);
-      const Q4 qa_ = ldq(sq + 4 * anc);
-      const int na = sanc[anc];
-      P = pa + qrot(qa_, P);
-      Q = qnormalized(qmul(qa_, Q));
-      anc = na;
-    }
-    __syncthreads();
-  }
+  // (1) stages A + B of k_dynamics: the pose of every body in its parent, then in the world by pointer doubling, left in sp / sq (fsim_kin.hpp)
+  V3 P;
+  Q4 Q;
+  const KinLane l = kin_joint_pose(a.kin, rec, b, &P, &Q);
+  kin_world_poses(a.kin, l, b, sp, sq, sanc, &P, &Q);
+  const bool on = l.on;
+  const int bb = l.bb;
   // stage C: inertial-frame origins, masses, the subtree masks from the ancestor masks (which carry the self bit), the tree's reference body
   const M3 R = q2m(Q);
   const float ms = on ? a.r_mass[bb] : 0.0f;
   const V3 ri = mulv(R, ldv3(a.r_ipos + 3 * bb));
-  if (b < a.nr) {
+  if (b < a.kin.nr) {
     stv3(sp + 3 * b, P);
     stq(sq + 4 * b, Q);
     stv3(sxi + 3 * b, P + ri);
     unsigned sub = 0;
-    for (int d = b; d < a.nr; d++)
+    for (int d = b; d < a.kin.nr; d++)
       if (b > 0 && (((unsigned)a.r_ancmask[d] >> b) & 1u)) sub |= 1u << d;
     ssub[b] = sub;
     sm[b] = ms;
@@ -93,7 +67,7 @@ __global__ __launch_bounds__(64) void k_momenta(MomArgs a, const float *__restri
   __syncthreads();
   // (2) the motion axes of every dof about the origin of its tree's first body (for a free part its own origin: no difference of positions)
   for (int d = b; d < a.nv; d += 64) {
-    const int db = sdb[d], djt = a.r_jtype[db], k = d - a.r_dofadr[db];
+    const int db = sdb[d], djt = a.kin.r_jtype[db], k = d - a.kin.r_dofadr[db];
     const V3 Pb = ldv3(sp + 3 * db), ref = ldv3(sp + 3 * sref[db]);
     const Q4 Qb = ldq(sq + 4 * db);
     S6 s;
@@ -103,9 +77,9 @@ __global__ __launch_bounds__(64) void k_momenta(MomArgs a, const float *__restri
       if (k < 3) s.l = ax;
       else { s.a = qrot(Qb, ax); s.l = cross(s.a, ref - Pb); }
     } else {
-      const V3 ax = qrot(Qb, ldv3(a.r_jaxis + 3 * db));
+      const V3 ax = qrot(Qb, ldv3(a.kin.r_jaxis + 3 * db));
       if (djt == JT_SLIDE) s.l = ax;
-      else { s.a = ax; s.l = cross(ax, ref - (Pb + qrot(Qb, ldv3(a.r_jpos + 3 * db)))); }
+      else { s.a = ax; s.l = cross(ax, ref - (Pb + qrot(Qb, ldv3(a.kin.r_jpos + 3 * db)))); }
     }
     sts6(scdof + 6 * d, s);
   }
@@ -113,16 +87,17 @@ __global__ __launch_bounds__(64) void k_momenta(MomArgs a, const float *__restri
   // every body's own joint twist, then the sum up its ancestors
   S6 u = s6zero();
   if (on) {
-    const float *qv = rec + a.qvel + da;
-    if (jt == JT_FREE) {
+    const int da = l.da;
+    const float *qv = rec + a.kin.qvel + da;
+    if (l.jt == JT_FREE) {
 #pragma unroll
       for (int k = 0; k < 6; k++) u = u + lds6(scdof + 6 * (da + k)) * qv[k];
     } else
       u = lds6(scdof + 6 * da) * qv[0];
   }
-  anc = on ? parent : 0;
-  for (int span = 1; span < a.maxdepth; span <<= 1) {
-    if (b < a.nr) { sts6(sU + 6 * b, u); sanc[b] = anc; }
+  int anc = l.anc;
+  for (int span = 1; span < a.kin.maxdepth; span <<= 1) {
+    if (b < a.kin.nr) { sts6(sU + 6 * b, u); sanc[b] = anc; }
     __syncthreads();
     if (anc > 0) {
       const S6 ua = lds6(sU + 6 * anc);
@@ -134,7 +109,7 @@ __global__ __launch_bounds__(64) void k_momenta(MomArgs a, const float *__restri
   }
   // per body: the velocity of its inertial origin, its own angular momentum (the product in the body frame, then turned), its energies
   float pe = 0.0f, ke = 0.0f;
-  if (b < a.nr) {
+  if (b < a.kin.nr) {
     const V3 xi = ldv3(sxi + 3 * b);
     const V3 off = (P - ldv3(sp + 3 * sref[b])) + ri; // x_b from the tree's reference point: for a free part 0 + ri, whatever its distance from the origin
     const V3 v = u.l + cross(u.a, off);
@@ -202,7 +177,7 @@ __global__ __launch_bounds__(64) void k_momenta(MomArgs a, const float *__restri
     const float pot = wave_sum(pe), kin = wave_sum(ke);
     float arm = 0.0f;
     for (int d = b; d < a.nv; d += 64) {
-      const float qd = rec[a.qvel + d];
+      const float qd = rec[a.kin.qvel + d];
       arm += 0.5f * a.dof_armature[d] * qd * qd;
     }
     arm = wave_sum(arm);
@@ -267,9 +242,8 @@ extern "C" int fsim_momenta(fsim_t *s, const fsim_momentum_out_t *out) {
   { int rc_ = settle(s); if (rc_) return rc_; } // the state fsim_sync leaves: overflowed envs re-stepped first
   const MomState &k = *s->mom;
   const DModel &m = s->m;
-  MomArgs ma{m.r_parent, m.r_jtype, m.r_qposadr, m.r_dofadr, m.r_ancmask, m.r_tree, m.dof_rbody, m.tree_bodyadr,
-             m.r_pos, m.r_quat, m.r_jaxis, m.r_jpos, m.r_mass, m.r_ipos, m.r_inertia, m.dof_armature, k.d_masks,
-             m.nr, m.maxdepth, m.nv, k.nsens, s->ly.stride, s->ly.qpos, s->ly.qvel, {m.gravity[0], m.gravity[1], m.gravity[2]}, *out};
+  MomArgs ma{kin_args(s), m.r_ancmask, m.r_tree, m.dof_rbody, m.tree_bodyadr, m.r_mass, m.r_ipos, m.r_inertia, m.dof_armature, k.d_masks,
+             m.nv, k.nsens, {m.gravity[0], m.gravity[1], m.gravity[2]}, *out};
   hipLaunchKernelGGL(k_momenta, dim3(s->n_envs), dim3(64), 0, s->stream, ma, s->d_state);
   HIPCHK(hipGetLastError());
   return FSIM_OK;
