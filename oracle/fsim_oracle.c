@@ -721,6 +721,23 @@ real osim_cost_at(osim_t *s, const real *qacc) {
 }
 /* signed distance of listed contact i (< 0: penetration), as data.contact[i].dist */
 real osim_contact_dist(osim_t *s, int i) { return (i >= 0 && i < s->ncon) ? s->contact[i].dist : 0.0; }
+/* listed contact i of the last forward pass, read only (see fsim_oracle.h): pos[3], frame[9], includemargin, mu, dim, whether it became a row,
+ * R of the normal row, aref[3], the row forces of the last solve [3], and their sum in the world frame: the force on geom 2's body */
+int osim_contact_info(osim_t *s, int i, real *out26) {
+  if (i < 0 || i >= s->ncon) return -1;
+  const Contact *k = &s->contact[i];
+  memset(out26, 0, 26 * sizeof(real));
+  memcpy(out26, k->pos, 3 * sizeof(real)); memcpy(out26 + 3, k->frame, 9 * sizeof(real));
+  out26[12] = k->includemargin; out26[13] = k->mu; out26[14] = k->dim; out26[15] = k->efc_address >= 0;
+  if (k->efc_address < 0) return 0;
+  const Row *r = &s->row[k->efc_address];
+  out26[16] = r->R;
+  for (int a = 0; a < k->dim && a < 3; a++) {
+    out26[17 + a] = r[a].aref; out26[20 + a] = r[a].force;
+    for (int c = 0; c < 3; c++) out26[23 + c] += k->frame[3 * a + c] * r[a].force;
+  }
+  return 0;
+}
 /* the narrow phase of one pair, outside any model (see fsim_oracle.h) */
 int osim_narrowphase(int t1, const real *p1, const real *R1, const real *s1, const real *verts1, int n1,
                      int t2, const real *p2, const real *R2, const real *s2, const real *verts2, int n2, real margin, real out[16][7]) {

@@ -26,7 +26,8 @@ extern "C" {
 
 /* `real` is the arithmetic type of the whole checker: double in libfsim_oracle.so / libfsim_cpu.so (THE checker), float in the
  * control build libfsim_cpu32.so (-DOSIM_REAL=float -fsingle-precision-constant, <tgmath.h>: the same source in fp32 throughout --
- * what `fp32 alone` does to a trajectory, scripts/divergence_control.py).  The Python binding (oracle/oracle_sim.py) is fp64 only. */
+ * what `fp32 alone` does to a trajectory, scripts/divergence_control.py).  The Python binding (oracle/oracle_sim.py) is fp64 unless asked:
+ * OracleSim(model, np.float32) binds the control build's osim_* entry points, for the per-contact read-out below. */
 #ifndef OSIM_REAL
 #define OSIM_REAL double
 #endif
@@ -58,6 +59,11 @@ int osim_contact_row(osim_t *, int i);
 int osim_row_info(osim_t *, int i, real *out8);
 real osim_row_dot(osim_t *, int i, const real *a);
 real osim_cost_at(osim_t *, const real *qacc);
+/* listed contact i of the last osim_forward / osim_step, in list order; reads only.  out26: pos[3], frame[9] (rows: the normal from geom 1 to
+ * geom 2, two tangents), includemargin, mu, dim, whether the contact became a row (dist < includemargin), R of the normal row, aref[3], the
+ * three row forces of the last solve (frame coordinates), the world force on geom 2's body (frame' f).  Everything after `became a row` is 0
+ * for a contact that did not.  -1: no such contact */
+int osim_contact_info(osim_t *, int i, real *out26);
 void osim_set_solver_kind(osim_t *, int kind); /* 0 = PGS (dual), 1 = Newton (primal, MuJoCo default) */
 
 /* The narrow phase of ONE pair of geoms, with no model behind it: types (MuJoCo's mjtGeom numbers), world positions, row-major rotation

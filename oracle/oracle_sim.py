@@ -14,6 +14,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_LIB32 = None
 
 
 def build(force=False):
@@ -24,34 +25,48 @@ def build(force=False):
     return so
 
 
+def lib32():
+    """the osim_* entry points of the float32 control build (libfsim_cpu32.so: the same source with real = float), for OracleSim(model, np.float32)"""
+    global _LIB32
+    if _LIB32 is None:
+        build()
+        _LIB32 = _declare(ctypes.CDLL(os.path.join(_HERE, "libfsim_cpu32.so")), ctypes.c_float)
+    return _LIB32
+
+
 def lib():
     global _LIB
     if _LIB is None:
-        L = ctypes.CDLL(os.environ.get("OSIM_LIB") or build())  # (OSIM_LIB: the sanitizer build, tests/test_oracle_sanitizers.py)
-        L.osim_create.restype = ctypes.c_void_p
-        L.osim_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-        L.osim_destroy.argtypes = [ctypes.c_void_p]
-        L.osim_last_error.restype = ctypes.c_char_p
-        L.osim_dptr.restype = ctypes.POINTER(ctypes.c_double)
-        L.osim_dptr.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
-        L.osim_iptr.restype = ctypes.POINTER(ctypes.c_int32)
-        L.osim_iptr.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
-        for f in ("osim_reset_data", "osim_forward"):
-            getattr(L, f).argtypes = [ctypes.c_void_p]
-            getattr(L, f).restype = None
-        L.osim_step.argtypes = [ctypes.c_void_p]
-        L.osim_step.restype = ctypes.c_int
-        L.osim_site_vel.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.osim_body_jac.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        L.osim_full_M.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        L.osim_set_solver.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
-        L.osim_set_solver_kind.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.osim_last_solver_iters.argtypes = [ctypes.c_void_p]
-        L.osim_last_solver_iters.restype = ctypes.c_int
-        L.osim_contact_dist.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.osim_contact_dist.restype = ctypes.c_double
-        _LIB = L
+        _LIB = _declare(ctypes.CDLL(os.environ.get("OSIM_LIB") or build()), ctypes.c_double)  # (OSIM_LIB: the sanitizer build, tests/test_oracle_sanitizers.py)
     return _LIB
+
+
+def _declare(L, c_real):
+    L.osim_create.restype = ctypes.c_void_p
+    L.osim_create.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+    L.osim_destroy.argtypes = [ctypes.c_void_p]
+    L.osim_last_error.restype = ctypes.c_char_p
+    L.osim_dptr.restype = ctypes.POINTER(c_real)
+    L.osim_dptr.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+    L.osim_iptr.restype = ctypes.POINTER(ctypes.c_int32)
+    L.osim_iptr.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+    for f in ("osim_reset_data", "osim_forward"):
+        getattr(L, f).argtypes = [ctypes.c_void_p]
+        getattr(L, f).restype = None
+    L.osim_step.argtypes = [ctypes.c_void_p]
+    L.osim_step.restype = ctypes.c_int
+    L.osim_site_vel.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    L.osim_body_jac.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.osim_full_M.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    L.osim_set_solver.argtypes = [ctypes.c_void_p, ctypes.c_int, c_real]
+    L.osim_set_solver_kind.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.osim_last_solver_iters.argtypes = [ctypes.c_void_p]
+    L.osim_last_solver_iters.restype = ctypes.c_int
+    L.osim_contact_dist.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.osim_contact_dist.restype = c_real
+    L.osim_contact_info.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    L.osim_contact_info.restype = ctypes.c_int
+    return L
 
 
 _NP_LIBS = {}
@@ -101,10 +116,16 @@ class _Views:
 
 
 class OracleSim:
-    def __init__(self, model):
-        """model: furniture_amd.mjcf.model.CompiledModel"""
+    def __init__(self, model, dtype=np.float64, lib_path=None):
+        """model: furniture_amd.mjcf.model.CompiledModel.  dtype float64: the checker; float32: the control build with real = float, whose views
+        and results are float32 (what fp32 alone does to a row; not a checker).  lib_path: another build of fsim_oracle.c with that `real`
+        (scripts/cone_defects.py: scratch copies with a deliberate defect)"""
         self.cm = model
-        L = lib()
+        self.dtype = np.dtype(dtype)
+        if lib_path is not None:
+            L = self._L = _declare(ctypes.CDLL(lib_path), ctypes.c_double if self.dtype == np.float64 else ctypes.c_float)
+        else:
+            L = self._L = lib() if self.dtype == np.float64 else lib32()
         blob = model.to_blob()
         self._h = L.osim_create(blob, len(blob))
         if not self._h:
@@ -135,28 +156,28 @@ class OracleSim:
 
     def _dview(self, name, shape=None):
         n = ctypes.c_int()
-        p = lib().osim_dptr(self._h, name.encode(), ctypes.byref(n))
+        p = self._L.osim_dptr(self._h, name.encode(), ctypes.byref(n))
         if not p:
             raise KeyError(name)
-        a = np.ctypeslib.as_array(p, shape=(max(n.value, 0),)) if n.value else np.zeros(0)
+        a = np.ctypeslib.as_array(p, shape=(max(n.value, 0),)) if n.value else np.zeros(0, self.dtype)
         return a.reshape(shape) if shape is not None and n.value else a
 
     def _iview(self, name):
         n = ctypes.c_int()
-        p = lib().osim_iptr(self._h, name.encode(), ctypes.byref(n))
+        p = self._L.osim_iptr(self._h, name.encode(), ctypes.byref(n))
         if not p:
             raise KeyError(name)
         return np.ctypeslib.as_array(p, shape=(max(n.value, 0),)) if n.value else np.zeros(0, np.int32)
 
     # -- mujoco_py-ish surface -------------------------------------------
     def reset(self):
-        lib().osim_reset_data(self._h)
+        self._L.osim_reset_data(self._h)
 
     def forward(self):
-        lib().osim_forward(self._h)
+        self._L.osim_forward(self._h)
 
     def step(self):
-        rc = lib().osim_step(self._h)
+        rc = self._L.osim_step(self._h)
         if rc:
             raise SimUnstable("oracle step rc=%d" % rc)
         if self._ndropped[0]:  # the checker never clips silently (fsim_oracle.c MAXCON / MAXEFC)
@@ -176,7 +197,19 @@ class OracleSim:
 
     def contact_dists(self):
         """data.contact[i].dist of the listed contacts (< 0: penetration)"""
-        return [lib().osim_contact_dist(self._h, i) for i in range(self.ncon)]
+        return [self._L.osim_contact_dist(self._h, i) for i in range(self.ncon)]
+
+    def contact_rows(self):
+        """the listed contacts of the last forward(), in list order, as a dict of float64 arrays: pos [n, 3], frame [n, 3, 3] (rows: the normal
+        from geom 1 to geom 2 and two tangents), includemargin, mu, dim, row (bool: the contact became a constraint row), R (of the normal row),
+        aref [n, 3], force [n, 3] (the row forces of the last solve, in the frame) and wforce [n, 3] (the world force on geom 2's body)"""
+        n = self.ncon
+        buf = np.zeros((n, 26), self.dtype)
+        for i in range(n):
+            assert self._L.osim_contact_info(self._h, i, buf[i].ctypes.data) == 0
+        b = buf.astype(np.float64)
+        return dict(pos=b[:, 0:3], frame=b[:, 3:12].reshape(n, 3, 3), includemargin=b[:, 12], mu=b[:, 13], dim=b[:, 14].astype(np.int64), row=b[:, 15] != 0,
+                    R=b[:, 16], aref=b[:, 17:20], force=b[:, 20:23], wforce=b[:, 23:26])
 
     def site_vel(self, site_id):
         """data.site_xvelp[site], data.site_xvelr[site] as mujoco_py computes them: jac(site) . qvel, i.e. the Jacobian
@@ -186,35 +219,35 @@ class OracleSim:
 
     def site_vel_cvel(self, site_id):
         """mj_objectVelocity-style: from the body velocities (cvel) of the last forward pass."""
-        vp, vr = np.zeros(3), np.zeros(3)
-        lib().osim_site_vel(self._h, int(site_id), vp.ctypes.data, vr.ctypes.data)
+        vp, vr = np.zeros(3, self.dtype), np.zeros(3, self.dtype)
+        self._L.osim_site_vel(self._h, int(site_id), vp.ctypes.data, vr.ctypes.data)
         return vp, vr
 
     def body_jac(self, body, point):
         nv = self.cm.nv
-        jp, jr = np.zeros((3, nv)), np.zeros((3, nv))
-        pt = np.ascontiguousarray(point, dtype=np.float64)
-        lib().osim_body_jac(self._h, int(body), pt.ctypes.data, jp.ctypes.data, jr.ctypes.data)
+        jp, jr = np.zeros((3, nv), self.dtype), np.zeros((3, nv), self.dtype)
+        pt = np.ascontiguousarray(point, dtype=self.dtype)
+        self._L.osim_body_jac(self._h, int(body), pt.ctypes.data, jp.ctypes.data, jr.ctypes.data)
         return jp, jr
 
     def full_M(self):
         nv = self.cm.nv
-        M = np.zeros((nv, nv))
-        lib().osim_full_M(self._h, M.ctypes.data)
+        M = np.zeros((nv, nv), self.dtype)
+        self._L.osim_full_M(self._h, M.ctypes.data)
         return M
 
     def set_solver(self, iterations=100, tolerance=1e-8, kind=None):
-        lib().osim_set_solver(self._h, int(iterations), float(tolerance))
+        self._L.osim_set_solver(self._h, int(iterations), float(tolerance))
         if kind is not None:
-            lib().osim_set_solver_kind(self._h, {"pgs": 0, "newton": 1}[kind])
+            self._L.osim_set_solver_kind(self._h, {"pgs": 0, "newton": 1}[kind])
 
     @property
     def last_solver_iters(self):
-        return lib().osim_last_solver_iters(self._h)
+        return self._L.osim_last_solver_iters(self._h)
 
     def close(self):
         if self._h:
-            lib().osim_destroy(self._h)
+            self._L.osim_destroy(self._h)
             self._h = None
 
     def __del__(self):

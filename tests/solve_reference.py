@@ -178,6 +178,9 @@ def put(osim, m, st, e, warm, iterations=200, tolerance=1e-14):
         mo.eq_data[:] = st["eq_data"][e].reshape(-1, 7)
         mo.eq_active[:] = st["eq_active"][e]
     mo.geom_contype[:], mo.geom_conaffinity[:] = st["geom_contype"][e], st["geom_conaffinity"][e]
+    if st.get("cursor") is not None:  # (the Cursor agent: its cursor bodies stand where the env's cursor says, as contacts_reference.set_state puts them)
+        for k, b in enumerate(m.arrays["cursor_bodyid"]):
+            mo.body_pos[int(b)] = st["cursor"][e][3 * k:3 * k + 3]
     osim.set_solver(iterations, tolerance, "newton")
 
 
@@ -283,7 +286,8 @@ def abi_solve(path, m, st, warm):
     n = len(st["qpos"])
     ws = st["qacc_warmstart"] if warm else np.zeros((n, m.nv))
     ses = Session(Abi(path), m.to_blob(), n, auto_reset=0)
-    write = lambda: ses.set_state(m, **dict({k: st[k] for k in cref.FIELDS if st[k].shape[1] > 0}, qacc_warmstart=ws))
+    more = dict(cursor=st["cursor"]) if st.get("cursor") is not None else {}
+    write = lambda: ses.set_state(m, **dict({k: st[k] for k in cref.FIELDS if st[k].shape[1] > 0}, qacc_warmstart=ws, **more))
     write()
     ses.forward()
     buf, sp = np.zeros((n, m.nv), np.float32), sim.StatePtrs()  # (qacc is not among the fields Session.get_state knows)
