@@ -379,7 +379,8 @@ template <class AngP> DEV bool env_is_aligned_core(V3 p1, const M3 &R1, V3 p2, c
     fwd_ok = true;
     float cs = env_cos(f1, f2);
     V3 k = normalized(up1);
-    float sn = sqrtf(1 - cs * cs);
+    // (clamped: parallel forward vectors give cs = 1 + 2^-23 in about every second frame, and the reference's sqrt of a negative number is NaN)
+    float sn = sqrtf(fmaxf(0.0f, 1 - cs * cs));
     V3 rp = cs * f1 + sn * cross(k, f1), rn = cs * f1 - sn * cross(k, f1);
     V3 fr = env_cos(rp, f2) > env_cos(rn, f2) ? rp : rn;
     stq(tq, env_lookat(up1, fr));
@@ -701,7 +702,7 @@ template <class Ctx> DEV void env_project_connector_quat(const Ctx &c, int k1, i
   const V3 up1 = colv(R1, 2), f1 = colv(R1, 1), f2 = colv(R2, 1), k = normalized(up1);
   V3 fr;
   if (!has_angle) {
-    const float cs = env_cos(f1, f2), sn = sqrtf(1 - cs * cs);
+    const float cs = env_cos(f1, f2), sn = sqrtf(fmaxf(0.0f, 1 - cs * cs)); // (clamped as in env_is_aligned_core)
     const V3 rp = cs * f1 + sn * cross(k, f1), rn = cs * f1 - sn * cross(k, f1);
     fr = env_cos(rp, f2) > env_cos(rn, f2) ? rp : rn;
   } else {

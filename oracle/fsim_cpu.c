@@ -153,7 +153,11 @@ static void rotate_vector(real *o, const real *v, const real *axis, real deg) {
 static void rotate_vector_cos(real *o, const real *v, const real *axis, real cs, int dir) {
   real k[3], c[3];
   unit_f32(k, axis); cross3(c, k, v);
-  for (int i = 0; i < 3; i++) o[i] = cs * v[i] + dir * sqrt(1 - cs * cs) * c[i];
+  real s2 = 1 - cs * cs;
+  /* the float64 checker restates the reference, NaN for cs > 1 included; the float32 control build clamps as the device does (csrc/fsim_env.hpp
+     env_is_aligned_core): there parallel forward vectors give cs > 1 in about every second frame */
+  if (sizeof(real) == 4 && s2 < 0) s2 = 0;
+  for (int i = 0; i < 3; i++) o[i] = cs * v[i] + dir * sqrt(s2) * c[i];
 }
 /* lookat_to_quat(forward, up) -> xyzw, then convert_quat(.., "wxyz"): returned wxyz here */
 static void lookat_wxyz(real *o, const real *forward, const real *up) {

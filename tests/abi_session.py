@@ -55,7 +55,11 @@ class Abi:
         if self.device is None:
             return np.zeros(shape, dtype=dtype)
         import torch
-        return torch.zeros(shape, dtype=getattr(torch, _NP2T[np.dtype(dtype).name]), device=self.device)
+        buf = torch.zeros(shape, dtype=getattr(torch, _NP2T[np.dtype(dtype).name]), device=self.device)
+        # torch fills the buffer on its own stream and the library writes it on the handle's non-blocking one: without this the fill can land
+        # after fsim_get_state's copy and zero the first rows of what was read (seen once per process, on a handle's first reads)
+        torch.cuda.synchronize()
+        return buf
 
     def put(self, buf, arr):
         if self.device is None:
