@@ -513,6 +513,7 @@ struct FlwState; // fsim_flow.hpp
 struct RayState; // fsim_rays.hpp
 struct ProbeState; // fsim_probes.hpp
 struct PairState; // fsim_pairs.hpp
+struct ClrState; // fsim_clearance.hpp
 struct FrameState; // fsim_frames.hpp
 struct DynState; // fsim_dynamics.hpp
 struct ConState; // fsim_contacts.hpp
@@ -603,6 +604,7 @@ struct fsim {
   RayState *ray = nullptr; // ray sensors: tables and pose scratch (fsim_set_rays): nothing is allocated or launched without them
   ProbeState *probe = nullptr; // distance probes: tables and pose scratch (fsim_set_probes): nothing is allocated or launched without them
   PairState *pair = nullptr; // geom-pair distance sensors: tables and pose scratch (fsim_set_pairs): nothing is allocated or launched without them
+  ClrState *clr = nullptr; // what-if clearance queries: tables and pose scratch (fsim_set_clearance): nothing is allocated or launched without them
   FrameState *frame = nullptr; // body / site frame sensors: the frame table (fsim_set_frames): nothing is allocated or launched without it
   DynState *dyn = nullptr; // mass matrix, inverse inertia and bias forces: the dof selection (fsim_set_dynamics): nothing is allocated or launched without it
   ConState *con = nullptr; // contact-force and touch sensors: the sensor table (fsim_set_contacts): nothing is allocated or launched without it
@@ -1723,6 +1725,7 @@ extern "C" int fsim_kernel_time_ms(fsim_t *s, double *avg_ms, int32_t *n) {
 #include "fsim_contacts.hpp"
 #include "fsim_wrench.hpp"
 #include "fsim_momentum.hpp"
+#include "fsim_clearance.hpp"
 
 // (below the sensor files: it frees their states, which are complete types only here)
 extern "C" void fsim_destroy(fsim_t *s) {
@@ -1737,6 +1740,7 @@ extern "C" void fsim_destroy(fsim_t *s) {
   sensor_free(s->ray);
   sensor_free(s->probe);
   sensor_free(s->pair);
+  sensor_free(s->clr);
   sensor_free(s->frame);
   sensor_free(s->dyn);
   sensor_free(s->con);

@@ -111,21 +111,28 @@ struct PairState {
   DevTables tabs; // owns them
 };
 
-extern "C" int fsim_set_pairs(fsim_t *s, int n_sensors, const fsim_pair_sensor_t *sensors) {
-  if (!s) FAIL(FSIM_EINVAL, "fsim_set_pairs: null handle");
-  if (n_sensors == 0) return sensor_clear(s, s->pair);
-  if (!sensors) FAIL(FSIM_EINVAL, "fsim_set_pairs: null argument");
-  if (n_sensors < 1 || n_sensors > FSIM_PAIR_MAX_SENSORS) FAIL(FSIM_EINVAL, "fsim_set_pairs: %d sensors (1 .. %d)", n_sensors, FSIM_PAIR_MAX_SENSORS);
+// What a set of pair sensors becomes on the host: the d_sens rows, the pair lists (A-major) and the static geom rows k_pair_dist stages,
+// with the words of one pose-scratch row.  Validated here for fsim_set_pairs and fsim_set_clearance (fsim_clearance.hpp) alike; who:
+// the caller's name for the messages.
+struct PairTables {
+  std::vector<float> srow, cg;
+  std::vector<int> pairs;
+  int pstride = 0;
+};
+
+static int pair_tables(const fsim *s, const char *who, int n_sensors, const fsim_pair_sensor_t *sensors, PairTables &pt) {
+  if (!sensors) FAIL(FSIM_EINVAL, "%s: null argument", who);
+  if (n_sensors < 1 || n_sensors > FSIM_PAIR_MAX_SENSORS) FAIL(FSIM_EINVAL, "%s: %d sensors (1 .. %d)", who, n_sensors, FSIM_PAIR_MAX_SENSORS);
   const DModel &m = s->m;
-  if (m.ncg > FSIM_CAM_MAX_GEOMS) FAIL(FSIM_EINVAL, "fsim_set_pairs: %d colliding geoms (the distance pass stages at most %d)", m.ncg, FSIM_CAM_MAX_GEOMS);
+  if (m.ncg > FSIM_CAM_MAX_GEOMS) FAIL(FSIM_EINVAL, "%s: %d colliding geoms (the distance pass stages at most %d)", who, m.ncg, FSIM_CAM_MAX_GEOMS);
   CamMountTables mt;
   { int rc_ = cam_mount_tables(s, mt); if (rc_) return rc_; }
   std::vector<int> madr, mnum; // convex-mesh colliders' slices of the hull-vertex table (absent = none)
   blob_i(s->blob, "cg_meshadr", madr); blob_i(s->blob, "cg_meshnum", mnum);
-  PairState c;
-  c.nsens = n_sensors;
-  std::vector<float> srow((size_t)PRW_WORDS * n_sensors, 0.0f);
-  std::vector<int> pairs;
+  std::vector<float> &srow = pt.srow, &cg = pt.cg;
+  std::vector<int> &pairs = pt.pairs;
+  srow.assign((size_t)PRW_WORDS * n_sensors, 0.0f);
+  pairs.clear();
   for (int i = 0; i < n_sensors; i++) {
     const fsim_pair_sensor_t &k = sensors[i];
     if (!(k.dmax > 0.0f) || !std::isfinite(k.dmax)) FAIL(FSIM_EINVAL, "pair sensor %d: needs 0 < dmax < inf (got %g)", i, k.dmax);
@@ -142,12 +149,12 @@ extern "C" int fsim_set_pairs(fsim_t *s, int n_sensors, const fsim_pair_sensor_t
     const size_t cnt = pairs.size() - first;
     if (cnt == 0) FAIL(FSIM_EINVAL, "pair sensor %d: no valid pair (every pair of its sides is a geom with itself or two planes)", i);
     if (cnt > FSIM_PAIR_MAX_PAIRS) FAIL(FSIM_EINVAL, "pair sensor %d: %zu pairs (at most %d per sensor)", i, cnt, FSIM_PAIR_MAX_PAIRS);
-    if (pairs.size() > FSIM_PAIR_MAX_TOTAL) FAIL(FSIM_EINVAL, "fsim_set_pairs: more than %d pairs over the set (sensor %d brings it to %zu)", FSIM_PAIR_MAX_TOTAL, i, pairs.size());
+    if (pairs.size() > FSIM_PAIR_MAX_TOTAL) FAIL(FSIM_EINVAL, "%s: more than %d pairs over the set (sensor %d brings it to %zu)", who, FSIM_PAIR_MAX_TOTAL, i, pairs.size());
     float *r = srow.data() + PRW_WORDS * i;
     r[PRW_DMAX] = k.dmax; r[PRW_FIRST] = cam_bits((int)first); r[PRW_COUNT] = cam_bits((int)cnt);
   }
   // the static rows of cam_geom_rows, with a hull's vertex slice where that has its plane slice
-  std::vector<float> cg((size_t)CAM_SW * m.ncg, 0.0f);
+  cg.assign((size_t)CAM_SW * m.ncg, 0.0f);
   std::vector<float> mvert;
   blob_f(s->blob, "mesh_vert", mvert);
   const size_t nvert = mvert.size() / 3;
@@ -157,20 +164,48 @@ extern "C" int fsim_set_pairs(fsim_t *s, int n_sensors, const fsim_pair_sensor_t
     r[3] = mt.cg_rbound[g];
     int adr = 0, num = 0;
     if (mt.cg_type[g] == GT_MESH) {
-      if ((size_t)g >= madr.size() || (size_t)g >= mnum.size()) FAIL(FSIM_EINVAL, "fsim_set_pairs: colliding geom %d is a convex mesh and the model has no hull vertices for it", g);
+      if ((size_t)g >= madr.size() || (size_t)g >= mnum.size()) FAIL(FSIM_EINVAL, "%s: colliding geom %d is a convex mesh and the model has no hull vertices for it", who, g);
       adr = madr[g]; num = mnum[g];
-      if (num < 4 || adr < 0 || (size_t)adr + num > nvert) FAIL(FSIM_EINVAL, "fsim_set_pairs: hull vertices of colliding geom %d out of range (%d + %d of %zu)", g, adr, num, nvert);
+      if (num < 4 || adr < 0 || (size_t)adr + num > nvert) FAIL(FSIM_EINVAL, "%s: hull vertices of colliding geom %d out of range (%d + %d of %zu)", who, g, adr, num, nvert);
     }
     r[4] = cam_bits(mt.cg_type[g]); r[5] = cam_bits(adr); r[6] = cam_bits(num); r[7] = cam_bits(mt.cg_orig[g]);
   }
-  c.npairs = (int)pairs.size();
-  c.pstride = (CAM_PW * m.ncg + 3) / 4 * 4;
+  pt.pstride = (CAM_PW * m.ncg + 3) / 4 * 4;
+  return FSIM_OK;
+}
+
+extern "C" int fsim_set_pairs(fsim_t *s, int n_sensors, const fsim_pair_sensor_t *sensors) {
+  if (!s) FAIL(FSIM_EINVAL, "fsim_set_pairs: null handle");
+  if (n_sensors == 0) return sensor_clear(s, s->pair);
+  PairTables pt;
+  { int rc_ = pair_tables(s, "fsim_set_pairs", n_sensors, sensors, pt); if (rc_) return rc_; }
+  PairState c;
+  c.nsens = n_sensors;
+  c.npairs = (int)pt.pairs.size();
+  c.pstride = pt.pstride;
   return sensor_install(s, "fsim_set_pairs", s->pair, c, [&](DevTables &t) {
-    t.put(&c.d_sens, srow.data(), srow.size());
-    t.put(&c.d_pairs, pairs.data(), pairs.size());
-    t.put(&c.d_cg, cg.data(), cg.size());
+    t.put(&c.d_sens, pt.srow.data(), pt.srow.size());
+    t.put(&c.d_pairs, pt.pairs.data(), pt.pairs.size());
+    t.put(&c.d_cg, pt.cg.data(), pt.cg.size());
     t.put(&c.d_pose, nullptr, (size_t)s->n_envs * std::max(c.pstride, 4));
   });
+}
+
+// One k_pair_dist launch over `rows` pose rows of `pose` (an env each for fsim_pair_distance, an (env, candidate) each for fsim_clearance);
+// the outputs are [rows][nsens]...
+static int pair_launch(fsim *s, const char *who, size_t rows, int nsens, int pstride, const float *pose, const float *d_cg, const float *d_sens, const int *d_pairs,
+                       float *dist_dev, int32_t *geoms_dev, float *fromto_dev, float *normal_dev) {
+  const DModel &m = s->m;
+  PairArgs ra{};
+  ra.ncg = m.ncg; ra.nsens = nsens; ra.pstride = pstride;
+  const size_t nunits = rows * nsens, nblk = (nunits + PAIR_WAVES - 1) / PAIR_WAVES;
+  if (nunits > 0x7fffffff) FAIL(FSIM_EINVAL, "%s: %zu units", who, nunits);
+  ra.nunits = (int)nunits;
+  const size_t lds = 4 * (size_t)PAIR_WAVES * CAM_GW * m.ncg; // at most 30 KB (96 geoms)
+  hipLaunchKernelGGL(k_pair_dist, dim3((unsigned)nblk), dim3(64 * PAIR_WAVES), lds, s->stream, ra, pose, d_cg, m.mesh_vert, d_sens, d_pairs, dist_dev, geoms_dev,
+                     fromto_dev, normal_dev);
+  HIPCHK(hipGetLastError());
+  return FSIM_OK;
 }
 
 extern "C" int fsim_pair_distance(fsim_t *s, float *dist_dev, int32_t *geoms_dev, float *fromto_dev, float *normal_dev) {
@@ -180,17 +215,7 @@ extern "C" int fsim_pair_distance(fsim_t *s, float *dist_dev, int32_t *geoms_dev
   HIPCHK(hipSetDevice(s->device));
   { int rc_ = settle(s); if (rc_) return rc_; } // the state fsim_sync leaves: overflowed envs re-stepped first
   const PairState &k = *s->pair;
-  const DModel &m = s->m;
   hipLaunchKernelGGL(k_cam_pose, dim3(s->n_envs), dim3(64), 0, s->stream, cam_pose_args(s, 0 /* no frames */, k.pstride), s->d_state, (const float *)nullptr, k.d_pose);
   HIPCHK(hipGetLastError());
-  PairArgs ra{};
-  ra.ncg = m.ncg; ra.nsens = k.nsens; ra.pstride = k.pstride;
-  const size_t nunits = (size_t)s->n_envs * k.nsens, nblk = (nunits + PAIR_WAVES - 1) / PAIR_WAVES;
-  if (nunits > 0x7fffffff) FAIL(FSIM_EINVAL, "fsim_pair_distance: %zu units", nunits);
-  ra.nunits = (int)nunits;
-  const size_t lds = 4 * (size_t)PAIR_WAVES * CAM_GW * m.ncg; // at most 30 KB (96 geoms)
-  hipLaunchKernelGGL(k_pair_dist, dim3((unsigned)nblk), dim3(64 * PAIR_WAVES), lds, s->stream, ra, k.d_pose, k.d_cg, m.mesh_vert, k.d_sens, k.d_pairs, dist_dev,
-                     geoms_dev, fromto_dev, normal_dev);
-  HIPCHK(hipGetLastError());
-  return FSIM_OK;
+  return pair_launch(s, "fsim_pair_distance", (size_t)s->n_envs, k.nsens, k.pstride, k.d_pose, k.d_cg, k.d_sens, k.d_pairs, dist_dev, geoms_dev, fromto_dev, normal_dev);
 }

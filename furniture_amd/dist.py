@@ -91,6 +91,8 @@ def step_wait_and_gather(sim, obs, reward, done, tag=0, stream=None, group=None)
     for f in ALL_SENSOR_FAMILIES:
         if getattr(sim, f.attr, None) is not None:
             raise NotImplementedError("step_wait_and_gather: %s are not part of the multi-GPU gather; %s them on each rank instead" % (f.gathered, f.verb))
+    if getattr(sim, "clearance_set", None) is not None:
+        raise NotImplementedError("step_wait_and_gather: clearance queries are not part of the multi-GPU gather; ask them on each rank instead")
     sim.sync()
     out = gather_observations(obs, reward, done, tag=tag, stream=stream, group=group)
     if stream is not None and obs.is_cuda:

@@ -389,9 +389,10 @@ class FurnitureBatchEnv:
     contacts = None
     wrenches = None
     momenta = None
+    clearance_set = None
 
     def __init__(self, agent, num_envs, config=None, device=0, first_env_index=0, auto_reset=True, dense=False, env_indices=None, obs_bf16=False,
-                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, contacts=None, wrenches=None, momenta=None, **kw):
+                 cameras=None, point_cloud=None, voxels=None, normals=None, flow=None, rays=None, probes=None, pairs=None, frames=None, dynamics=None, contacts=None, wrenches=None, momenta=None, clearance=None, **kw):
         """dense=True: FurnitureSawyerDenseRewardEnv semantics (furniture_sawyer_dense.py) -- the config then carries the
         config/furniture_sawyer_dense.py overrides and, optionally, any of its reward coefficients.
         obs_bf16=True: the observation slab is stored (and returned) as bfloat16 -- state and arithmetic stay float32.
@@ -454,7 +455,10 @@ class FurnitureBatchEnv:
         momenta: a furniture_amd.momentum.MomentumSet (needs none of the others) -- the observations then also hold mom_com, mom_linvel
         and mom_angmom (float32 [n, S, 3]: the centre of mass of each sensor's set of bodies, its velocity and the set's angular momentum
         about it, world frame, at the state the observation describes) and, with jacobian=True / energy=True in the set, mom_jac (float32
-        [n, S, 3, nv], mom_linvel = mom_jac @ qvel) and mom_energy (float32 [n, 2], potential then kinetic), from one fsim_momenta call."""
+        [n, S, 3, nv], mom_linvel = mom_jac @ qvel) and mom_energy (float32 [n, 2], potential then kinetic), from one fsim_momenta call.
+        clearance: a furniture_amd.clearance.ClearanceSet (needs none of the others) -- NOT an observation: nothing is added to the
+        observation dict or to observation_space.  It is the set env.clearance(cand, carry_mask) evaluates: what the set's pair sensors
+        would read at candidate joint configurations, without touching the state."""
         if point_cloud is not None:
             from .points import check
             check(point_cloud, list(cameras) if cameras else None)
@@ -471,6 +475,9 @@ class FurnitureBatchEnv:
         for f in ALL_SENSOR_FAMILIES:
             if sensors[f.kw] is not None:
                 importlib.import_module("." + f.module, __package__).check(sensors[f.kw])
+        if clearance is not None:
+            from .clearance import check as check_clearance
+            check_clearance(clearance)
         cfg = config if config is not None else make_config(**(DENSE_OVERRIDES if dense else {}))
         for k, v in kw.items():
             setattr(cfg, k, v)
@@ -592,6 +599,19 @@ class FurnitureBatchEnv:
             if sensors[f.kw] is not None:
                 getattr(self.sim, f.set)(sensors[f.kw])
                 setattr(self, f.buf, {k: torch.empty((num_envs,) + sh, dtype=dt, device=dev) for k, (sh, dt) in getattr(self.sim, f.shapes)().items()})
+        self.clearance_set = clearance
+        if clearance is not None:  # (not an observation: no buffers, and nothing is launched before env.clearance is called)
+            self.sim.set_clearance(clearance)
+
+    def clearance(self, cand, carry_mask=None):
+        """What the pair sensors of the env's ClearanceSet would read at K candidate configurations per env (FSim.clearance): cand a
+        float32 device tensor [n, K, D] over the set's dofs, carry_mask None or a uint8 device tensor [n] (bit r = carry rule r) -> dict
+        of new device tensors clearance_distance [n, K, S], clearance_geoms [n, K, S, 2], clearance_valid [n, K] and, when the set asks
+        for them, clearance_fromto [n, K, S, 6] and clearance_normal [n, K, S, 3].  Reads the state the last reset() / step() left and
+        writes none of it."""
+        if self.clearance_set is None:
+            raise ValueError("clearance: the env has no clearance set (FurnitureBatchEnv(..., clearance=ClearanceSet(...)))")
+        return self.sim.clearance(cand, carry_mask)
 
     # -- spaces (furniture.py:215-310, furniture_sawyer.py:28-64) ---------------------------------------
     @property
@@ -1043,7 +1063,7 @@ class _SingleEnv:
             old.close()
             self._b = FurnitureBatchEnv(self._agent, 1, config=cfg, device=dev, auto_reset=False, dense=self._dense, cameras=old.cameras,
                                          point_cloud=old.point_cloud, voxels=old.voxels, normals=old.normals, flow=old.flow,
-                                         **{f.kw: getattr(old, f.kw) for f in ALL_SENSOR_FAMILIES})
+                                         clearance=old.clearance_set, **{f.kw: getattr(old, f.kw) for f in ALL_SENSOR_FAMILIES})
             self._b._sampler.rngs = rngs
             self._b._sampler.hist = [[] for _ in rngs]
         return self._np(self._b.reset())

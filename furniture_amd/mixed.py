@@ -57,6 +57,9 @@ class FurnitureMixedBatchEnv:
             if kw.pop(f.kw, None) is not None:
                 raise NotImplementedError("%s= is not supported by the mixed-furniture batch (one %s per FurnitureBatchEnv): "
                                           "make one FurnitureBatchEnv per furniture instead" % (f.kw, f.one))
+        if kw.pop("clearance", None) is not None:
+            raise NotImplementedError("clearance= is not supported by the mixed-furniture batch (one clearance set per FurnitureBatchEnv): "
+                                      "make one FurnitureBatchEnv per furniture instead")
         cfg = config if config is not None else make_config()
         for key, v in kw.items():
             setattr(cfg, key, v)

@@ -72,6 +72,11 @@ class FsimPairSensor(ctypes.Structure):
     _fields_ = [("a", ctypes.c_uint32 * 3), ("b", ctypes.c_uint32 * 3), ("dmax", ctypes.c_float)]
 
 
+class FsimClrCarry(ctypes.Structure):
+    """fsim_clr_carry_t (include/fsim_clearance.h)"""
+    _fields_ = [("part_body", ctypes.c_int32), ("carrier_body", ctypes.c_int32)]
+
+
 class FsimFrame(ctypes.Structure):
     """fsim_frame_t (include/fsim_frames.h)"""
     _fields_ = [("body", ctypes.c_int32), ("pos", ctypes.c_float * 3), ("quat", ctypes.c_float * 4)]
@@ -123,7 +128,7 @@ def library_path():
 def build(force=False, verbose=False):
     """Compile libfsim.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h", "fsim_contacts.h", "fsim_wrench.h", "fsim_momentum.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("fsim.h", "fsim_camera.h", "fsim_points.h", "fsim_voxels.h", "fsim_normals.h", "fsim_flow.h", "fsim_rays.h", "fsim_probes.h", "fsim_pairs.h", "fsim_frames.h", "fsim_dynamics.h", "fsim_contacts.h", "fsim_wrench.h", "fsim_momentum.h", "fsim_clearance.h")]
     # the host helper is a library of its own with its own staleness: a checkout that has libfsim.so but no (or an old) libfsim_host.so
     # must not silently run the 100x slower Python sampler
     host_so, host_c = os.path.join(_CSRC, "libfsim_host.so"), os.path.join(_CSRC, "fsim_host.c")
@@ -245,6 +250,8 @@ def lib():
         L.fsim_wrenches.argtypes = [ctypes.c_void_p, ctypes.POINTER(FsimWrenchOut)]
         L.fsim_set_momenta.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.fsim_momenta.argtypes = [ctypes.c_void_p, ctypes.POINTER(FsimMomentumOut)]
+        L.fsim_set_clearance.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.fsim_clearance.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 7
         _LIB = L
     return _LIB
 
@@ -284,6 +291,8 @@ CONTACT_SYMBOLS = ["fsim_set_contacts", "fsim_contact_forces"]
 WRENCH_SYMBOLS = ["fsim_set_wrenches", "fsim_wrenches"]
 # the momentum-sensor entry points: a header of their own (include/fsim_momentum.h), exported by the same library
 MOMENTUM_SYMBOLS = ["fsim_set_momenta", "fsim_momenta"]
+# the clearance-query entry points: a header of their own (include/fsim_clearance.h), exported by the same library
+CLEARANCE_SYMBOLS = ["fsim_set_clearance", "fsim_clearance"]
 
 
 def preassembled_rows(model, preassembled):
@@ -896,6 +905,55 @@ class FSim:
             raise FsimError("pair_distance: no pair set (FSim.set_pairs)")
         res = self._sensor_outputs("pair_distance", self.pair_shapes(), out)
         self._sensor_call(lib().fsim_pair_distance, *self._ptrs(res, ("pair_distance", "pair_geoms", "pair_fromto", "pair_normal")))
+        return res
+
+    # -- what-if clearance queries (include/fsim_clearance.h, furniture_amd/clearance.py) -------------------------------------------------
+    clearance_set = None
+
+    def set_clearance(self, spec):
+        """Replace the handle's clearance set (a furniture_amd.clearance.ClearanceSet; None clears it); checked on the host first, then by
+        the library.  Independent of the pair set and of every sensor family: needs and disturbs none of them."""
+        from .clearance import ClearanceSet, clearance_tables
+
+        def install():
+            dofs, tab, carry = clearance_tables(self.cm, spec)
+            self._chk(lib().fsim_set_clearance(self._h, len(dofs), dofs.ctypes.data, len(tab), ctypes.addressof(tab), len(carry) if carry is not None else 0,
+                                               ctypes.addressof(carry) if carry is not None else None, spec.max_candidates, spec.scratch_rows))
+        self._set_sensors(lib().fsim_set_clearance, "clearance_set", spec, ClearanceSet, install)
+
+    def clearance_shapes(self, K):
+        """{key: (shape, dtype)} of clearance's outputs for K candidates per env (without the n_envs dimension)"""
+        if self.clearance_set is None:
+            raise FsimError("clearance_shapes: no clearance set (FSim.set_clearance)")
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= self.clearance_set.max_candidates:
+            raise ValueError("clearance: K = %r candidates (1 .. max_candidates = %d)" % (K, self.clearance_set.max_candidates))
+        return {k: (sh, getattr(self.torch, dt)) for k, (sh, dt) in self.clearance_set.shapes(int(K)).items()}
+
+    def clearance(self, cand, carry_mask=None, out=None):
+        """The clearance of K candidate configurations per env (include/fsim_clearance.h), for the state sync() leaves.  cand: a contiguous
+        float32 device tensor [n, K, D], D the dofs of the clearance set in its order; carry_mask: None (nothing is carried) or a
+        contiguous uint8 device tensor [n], bit r = carry rule r -> dict of device tensors: clearance_distance (float32 [n, K, S]),
+        clearance_geoms (int32 [n, K, S, 2]), clearance_valid (uint8 [n, K], 0 = the candidate held a value that is not finite, and the
+        env's own value stood in for it) and, when the set asks for them, clearance_fromto (float32 [n, K, S, 6]) and clearance_normal
+        (float32 [n, K, S, 3]), each what pair_distance would give with the set's sensors if the env's qpos held the candidate.  Writes
+        no state.  out: a dict of such tensors to write into instead of new ones; a key that is there alone is computed alone (at least
+        one besides clearance_valid).  Ordered with torch's current stream both ways."""
+        torch = self.torch
+        spec = self.clearance_set
+        if spec is None:
+            raise FsimError("clearance: no clearance set (FSim.set_clearance)")
+        if not isinstance(cand, torch.Tensor) or cand.dtype != torch.float32 or cand.dim() != 3 or cand.shape[0] != self.n_envs or cand.shape[2] != spec.n_dofs \
+                or not cand.is_contiguous() or cand.device != self.device:
+            raise ValueError("clearance: cand is not a contiguous float32 tensor of shape (%d, K, %d) on %s" % (self.n_envs, spec.n_dofs, self.device))
+        K = int(cand.shape[1])
+        if carry_mask is not None and (not isinstance(carry_mask, torch.Tensor) or carry_mask.dtype != torch.uint8 or tuple(carry_mask.shape) != (self.n_envs,)
+                                       or not carry_mask.is_contiguous() or carry_mask.device != self.device):
+            raise ValueError("clearance: carry_mask is not a contiguous uint8 tensor of shape (%d,) on %s" % (self.n_envs, self.device))
+        res = self._sensor_outputs("clearance", self.clearance_shapes(K), out)
+        if all(k == "clearance_valid" for k in res):
+            raise ValueError("clearance: out holds clearance_valid alone (at least one of the distance, geoms, fromto and normal outputs)")
+        self._sensor_call(lib().fsim_clearance, K, cand.data_ptr(), carry_mask.data_ptr() if carry_mask is not None else None,
+                          *self._ptrs(res, ("clearance_distance", "clearance_geoms", "clearance_fromto", "clearance_normal", "clearance_valid")))
         return res
 
     # -- body and site frame sensors with their Jacobians (include/fsim_frames.h, furniture_amd/frames.py) --------------------------------

@@ -61,6 +61,9 @@ class FurnitureVecEnv:
             if kw.pop(f.kw, None) is not None:
                 raise NotImplementedError("%s= is not supported by the VecEnv wrapper (its observations are host numpy arrays): use "
                                           "FurnitureBatchEnv(..., %s=%s(...)), whose %s outputs stay on the device" % (f.kw, f.kw, f.cls, f.noun))
+        if kw.pop("clearance", None) is not None:
+            raise NotImplementedError("clearance= is not supported by the VecEnv wrapper (its surface is host numpy arrays): use "
+                                      "FurnitureBatchEnv(..., clearance=ClearanceSet(...)), whose candidates and answers stay on the device")
         if config is not None:
             kw.update(config.__dict__)
         cls = REGISTRY[name]
